@@ -7,11 +7,19 @@ A step = everything the reference's training step does: staging of
 student (6 views + originals) and teacher (2 views) encoders, projections, DINO + MSE losses,
 centre update, teacher EMA, full backward, gradient all-reduce (N>1), Adam.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank/GPU)
 
 Rank 0 prints ONE JSON line.  Inputs are synthetic AVMNIST-shaped tensors (pixel values
 randint(0,256)/255) generated on the device before the timed region; weights random-init.
+Every generator is seeded, so the same arguments give the same inputs in every run.
+
+A plain run sets up, warms up (the step's capture included), times the K steps and prints the
+line.  --full adds everything else the bench can measure: the per-launch rooflines (a timed
+eager warm-up step, in-graph span marks on the watched launches, eager and isolated replays
+after the timed region) and the CPU baseline.  --dump-outputs DIR writes what the last timed
+step left its caller (the loss it returned, the parameters, gradients and buffers of the store)
+as DIR/<name>.npy, for comparing two builds output for output.
 """
 import argparse
 import json
@@ -57,7 +65,16 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "fp8"],
                     help="fp8: the mid-layer convs' forward, input gradient and weight gradient "
                          "on the block-scaled e4m3 MFMA (config 5); maps stored bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the per-launch rooflines (\"roofline\", \"roofline_hbm\": "
+                         "instrumented warm-up, span marks in the timed steps, eager and isolated "
+                         "replays after them) and the CPU baseline (\"cpu_baseline\")")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's results (loss, student / "
+                         "teacher parameters, gradients, buffers) to DIR/<name>.npy (float32; "
+                         "arrays over the size budget as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--no-graph", action="store_true",
                     help="launch every kernel from Python each step instead of replaying the "
                          "captured hipGraph of the step")
@@ -347,6 +364,38 @@ def _cpu_baseline(batch, seconds, host):
                       f"{torch.get_num_threads()} threads, one per physical core"}
 
 
+DUMP_MAX_ELEMS = 2 << 20      # per array (8 MiB of float32): five arrays stay far below 64 MB
+
+
+def snapshot_outputs(eng, loss):
+    """What the step just run left its caller, as float32 host arrays: the loss tensor step()
+    returned and the store it updated (student and teacher parameter arenas, the gradient
+    arena, the BN running statistics + DINO centre arena).  An arena above DUMP_MAX_ELEMS is
+    reduced to a fixed sample (sorted indices drawn with seed 0: the same elements in every run
+    and every build, since the arena layout follows the model spec alone)."""
+    import numpy as np
+    st = eng.store
+    named = {"loss": loss.reshape(1), "student": st.student, "teacher": st.teacher,
+             "grad": st.grad, "buffers": st.buf_arena}
+    out = {}
+    for name, t in named.items():
+        if t is None:
+            continue
+        a = t.detach().to("cpu", torch.float32).numpy().reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a[idx]
+        out[name] = np.array(a, dtype=np.float32)       # (a copy: later steps leave it alone)
+    return out
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -382,10 +431,13 @@ def main():
             return eng.step(pool[i % len(pool)], next_batch=pool[(i + 1) % len(pool)])
         return eng.step(pool[i % len(pool)])
 
-    # warm-up: eager steps (the second one times every instrumented kernel to find the dominant
-    # one; the first one's launches are cold), then -- graph mode -- the step's capture
-    # graph replay needs one eager warm-up step (it sizes every workspace) and the capture
-    # inside the warm-up: with fewer than 2 warm-up steps the bench runs eagerly
+    # warm-up: eager steps (with --full the second one times every instrumented kernel to find
+    # the dominant one; the first one's launches are cold), then -- graph mode -- the step's
+    # capture.  graph replay needs one eager warm-up step (it sizes every workspace) and the
+    # capture inside the warm-up: with fewer than 2 warm-up steps the bench runs eagerly.
+    # The launch instrumentation (KernelTimer / SpanTimer) belongs to --full and to the
+    # --probe-dominant replay; a plain run launches nothing but its steps
+    instrument = args.full or bool(args.probe_dominant)
     use_graph = not args.no_graph and not args.probe_dominant and args.warmup >= 2
     eng.use_graph = use_graph
     eng.graph.warmup = min(2, max(args.warmup - 1, 0))
@@ -394,7 +446,7 @@ def main():
     # the timed warm-up step must run eagerly: with graphs, calls >= graph.warmup capture (and
     # events recorded inside a capture have no timestamps)
     t_idx = min(1, args.warmup - 1)
-    if use_graph and t_idx >= eng.graph.warmup:
+    if not instrument or (use_graph and t_idx >= eng.graph.warmup):
         t_idx = -1
     dominant = hbm_dom = watch = None
 
@@ -475,7 +527,7 @@ def main():
                 eng.step(pool[0], mode=m)
     if dominant is None and watch is None and wtimer is not None:
         summ, dominant, hbm_dom, watch = pick_watch()
-    ops.TIMER = None if use_graph else ops.KernelTimer(only=watch)
+    ops.TIMER = None if use_graph or not instrument else ops.KernelTimer(only=watch)
 
     if args.probe_dominant:
         ops.TIMER = ops.KernelTimer(only=dominant)
@@ -513,6 +565,46 @@ def main():
     lv = loss.item()
     if not math.isfinite(lv):
         raise SystemExit(f"non-finite loss {lv}")
+    # (before anything below steps the engine again)
+    dumped = snapshot_outputs(eng, loss) if args.dump_outputs and rank == 0 else None
+
+    total_pairs = world * B * args.steps
+    value = total_pairs / elapsed
+    out = {
+        "metric": METRIC, "value": round(value, 2), "unit": "pairs/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed * 1e3 / args.steps, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
+        "data": "synthetic: randint(0,256)/255 AVMNIST-shaped views resident in HBM; random-init weights",
+        "config": {"workload": workload,
+                   "model": model, "global_batch": world * B, "seq_len": None,
+                   "parallelism": f"dp{world}"},
+        "full": args.full,
+    }
+    if args.full:
+        out.update(launch_rooflines(args, eng, ops, step, last, spans, use_graph, watch, dominant,
+                                    hbm_dom, elapsed))
+    out.update(step_summary(args, world, value, elapsed, t_issue, use_graph, eng, lv))
+    if args.probe:
+        if args.workload != "dino" or args.mode != "semi_supervised":
+            raise SystemExit("--probe: the epoch-end probe is timed for --mode semi_supervised (config 5)")
+        out["probe"] = time_probe(eng, args, device, act, rank)
+    cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    if cpu and args.workload == "dino" and args.mode == "mse":
+        out["cpu_baseline"] = cpu_baseline(args.cpu_batch, args.cpu_seconds)
+    elif cpu and args.workload == "uni":
+        out["cpu_baseline"] = cpu_baseline_uni(B, args.cpu_seconds)
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def launch_rooflines(args, eng, ops, step, last, spans, use_graph, watch, dominant, hbm_dom, elapsed):
+    """--full: the "roofline" / "roofline_hbm" entries of the line, from the span marks the
+    timed steps carried plus eager and isolated replays of the watched launches run here."""
     in_graph = spans.read() if spans is not None else {}
     ops.SPANS = None
     if use_graph:
@@ -593,9 +685,11 @@ def main():
             r["isolated_avg_launch_us"] = round(iso, 2)
             r["isolated_achieved"] = round(ach, 2)
             r["isolated_frac"] = round(ach / r["peak"], 4)
+    return {"roofline": roof, "roofline_hbm": roof_hbm}
 
-    total_pairs = world * B * args.steps
-    value = total_pairs / elapsed
+
+def step_summary(args, world, value, elapsed, t_issue, use_graph, eng, lv):
+    """The entries of the line computed from the timed region alone (no further GPU work)."""
     # whole-step roofline (SURVEY 8(d)): pairs/s per GPU against min(HBM ceiling, MFMA ceiling)
     key = args.mode if args.workload == "dino" else args.workload
     bpp = STEP_BYTES_PER_PAIR_BF16[key] * (2 if args.dtype == "f32" else 1)
@@ -610,17 +704,7 @@ def main():
                  "achieved_TFLOPs": round(per_gpu * fpp / 1e12, 2),
                  "frac": round(per_gpu / min(ceil_hbm, ceil_mfma), 4),
                  "traffic_bytes_per_pair": load_traffic(args.traffic, "step:" + key)}
-    out = {
-        "metric": METRIC, "value": round(value, 2), "unit": "pairs/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed * 1e3 / args.steps, 3), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
-        "data": "synthetic: randint(0,256)/255 AVMNIST-shaped views resident in HBM; random-init weights",
-        "config": {"workload": workload,
-                   "model": model, "global_batch": world * B, "seq_len": None,
-                   "parallelism": f"dp{world}"},
-        "roofline": roof,
-        "roofline_hbm": roof_hbm,
+    return {
         "step_roofline": step_roof,
         "timed_region_s": round(elapsed, 4),
         "host_issue_ms_per_step": round(t_issue * 1e3 / args.steps, 3),
@@ -628,19 +712,6 @@ def main():
         "teacher_pipelined": bool(getattr(eng, "pipeline", False)),
         "final_loss": round(lv, 6),
     }
-    if args.probe:
-        if args.workload != "dino" or args.mode != "semi_supervised":
-            raise SystemExit("--probe: the epoch-end probe is timed for --mode semi_supervised (config 5)")
-        out["probe"] = time_probe(eng, args, device, act, rank)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "dino" \
-            and args.mode == "mse":
-        out["cpu_baseline"] = cpu_baseline(args.cpu_batch, args.cpu_seconds)
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "uni":
-        out["cpu_baseline"] = cpu_baseline_uni(B, args.cpu_seconds)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":
