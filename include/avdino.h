@@ -225,6 +225,14 @@ int avd_cl_conv_wgrad(const void* x, const void* dy, int dt, float* dw_parts, in
 int avd_cl_bn_relu_pool(const void* y, int dt, const float* scale, const float* shift, void* out,
                         int mode, int N, int B, int C, int H, int W, void* stream);
 
+/* The mode-0 bf16 call above that also keeps the backward's routing: codes [N][H/2][W/2][C/8]
+ * u32, one word per (pooled pixel, channel octet q); nibble e = 1 + the first-max argmax (window
+ * order (0,0), (0,1), (1,0), (1,1)) of channel 8q + e where the window's max is > 0, else 0 --
+ * avd_cl_bn_bwd_apply's routing rule, for avd_cl_layer_bwd_codes.  out is bit-identical to
+ * avd_cl_bn_relu_pool's; codes == NULL stores none. */
+int avd_cl_bn_relu_pool_codes(const void* y, const float* scale, const float* shift, void* out,
+                              unsigned* codes, int N, int B, int C, int H, int W, void* stream);
+
 /* Backward of the block above, given gout (mode 0: NHWC dt; mode 1: [N,C] f32; mode 2: f32 in
  * the mode-2 layout).  reduce: parts [C][G][R][2], R = avd_cl_bn_bwd_rows(...), then
  * avd_bn_bwd_finalize -> coef; apply: dy [N,H,W,C] (dt) = k1*dz + kx*y + k0. */
@@ -286,6 +294,14 @@ int avd_cl_layer_bwd(const void* y, const void* gout, const float* scale, const 
                      const float* coef, const void* dy, const void* x, const void* wk_d, void* dx,
                      float* parts, int slabs, int dt, int N, int B, int Cin, int H, int W, int Cout,
                      int K, int pad, void* stream);
+
+/* avd_cl_layer_bwd from y with the gradient routed by the forward's avd_cl_bn_relu_pool_codes
+ * words instead of a recomputed relu(bn(y)) argmax: dy_k = k1 * (code == k + 1 ? gout : 0) +
+ * (kx * y_k + k0), the same two FMAs -- dx and parts bit-identical to avd_cl_layer_bwd's for the
+ * same slabs when codes came from the same y, scale and shift.  Neither scale nor shift is read. */
+int avd_cl_layer_bwd_codes(const void* y, const void* gout, const unsigned* codes, const float* coef,
+                           const void* x, const void* wk_d, void* dx, float* parts, int slabs, int dt,
+                           int N, int B, int Cin, int H, int W, int Cout, int K, int pad, void* stream);
 
 /* The partial sums of avd_cl_bn_bwd_reduce (same rows and layout, for avd_bn_bwd_finalize)
  * from the POOLED output p = maxpool2(relu(y*scale + shift)) instead of y: at the window's

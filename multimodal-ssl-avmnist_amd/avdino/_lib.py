@@ -61,6 +61,7 @@ PROTOS = {
     "avd_mark": [P, I, P],
     "avd_mark_span": [P, I, I, P],
     "avd_cl_bn_relu_pool": [P, I, P, P, P, I, I, I, I, I, I, P],
+    "avd_cl_bn_relu_pool_codes": [P, P, P, P, P, I, I, I, I, I, P],
     "avd_cl_bn_bwd_rows": [I, I, I, I, I],
     "avd_cl_bn_bwd_reduce": [P, I, P, I, P, P, P, P, P, I, I, I, I, I, P],
     "avd_cl_bn_bwd_apply": [P, I, P, I, P, P, P, P, I, I, I, I, I, P],
@@ -74,6 +75,7 @@ PROTOS = {
     "avd_xent_fused": [P, P, I, I, I, I, I, I, I, I, F, F, P, P, P, P, L, P],
     "avd_cl_layer_bwd_slabs": [I, I, I, I, I, I, I, I],
     "avd_cl_layer_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
+    "avd_cl_layer_bwd_codes": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     "avd_sum_rows": [P, I, I, L, P, I, P],
     "avd_sum_rows_chunks": [I, I],
     "avd_sum_rows_split": [P, I, I, L, P, I, P, L, P],

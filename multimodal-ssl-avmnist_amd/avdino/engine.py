@@ -234,7 +234,7 @@ class ConvBranch:
         B = N // G
         if wts is None:
             wts = self.prepare(ws, store, tag, need_dgrad, N, B)
-        ctx = {"x": [x], "y": [], "stats": [], "wts": wts, "N": N, "G": G}
+        ctx = {"x": [x], "y": [], "stats": [], "wts": wts, "N": N, "G": G, "pool_codes": {}}
         h = x
         nl = len(self.stack.convs)
         for i, (ci, co, k, pad) in enumerate(self.stack.convs):
@@ -271,6 +271,11 @@ class ConvBranch:
                 # BN -> ReLU -> pool from the conv recomputed out of x (bit-identical y)
                 ops.cl_c1_recompute(ops.C1_APPLY, h, wts[0][0], store[self.stack.conv_keys[0] + ".bias"],
                                     N, B, ci, H, H, co, k, pad, scale=st[2], shift=st[3], z=out)
+            elif self.LAYER_BWD_CODES and self._layer_bwd_slabs(i, N, B, mode, wts[i]):
+                # this layer's backward is the fused launch: keep the pool's routing for it
+                codes = ws.get(f"{tag}.pc{i}", N * Hp * Hp * co // 8, torch.int32)
+                ops.cl_bn_relu_pool_codes(y, st[2], st[3], out, codes, N, B, co, Ho, Ho)
+                ctx["pool_codes"][i] = codes
             else:
                 ops.cl_bn_relu_pool(y, st[2], st[3], out, mode, N, B, co, Ho, Ho)
             if i < nl - 1:
@@ -526,6 +531,21 @@ class ConvBranch:
     # the audio conv2 (56^2) backward as ONE launch (avd_cl_layer_bwd: BN-backward apply, input
     # and weight gradient from the same staged tiles, no dY in HBM); False: apply + dgrad + wgrad
     LAYER_BWD = True
+    # that launch routes the pooled gradient by the forward pool's argmax codes
+    # (avd_cl_bn_relu_pool_codes) instead of recomputing relu(bn(y)) per window; False: recompute
+    LAYER_BWD_CODES = True
+
+    def _layer_bwd_slabs(self, i, N, B, mode, wt):
+        """Slabs of layer i's fused backward launch, 0 where the layer takes the separate
+        launches: the one predicate of forward (which keeps the routing codes for it) and
+        backward.  (The fused layer's BN-backward apply holds at most ops.APPLY_GMAX groups'
+        coefficients, e.g. not 2 + 7 views.)"""
+        ci, co, k, pad = self.stack.convs[i]
+        H = self.dims[i][0]
+        if not (self.LAYER_BWD and i > 0 and mode == 0 and wt[1] is not None and wt[3] is None
+                and N // B <= ops.APPLY_GMAX and not self._mx_wgrad(i, N)):
+            return 0
+        return ops.cl_layer_bwd_slabs(self.act, N, ci, H, H, co, k, pad)
 
     def backward(self, ws, store, ctx, dfeat, wstream=None):
         """dfeat: gradient of the features (f32 [N, F]; hwc: NHWC act dtype); writes conv/BN
@@ -563,11 +583,7 @@ class ConvBranch:
                                 store.grad_of(ck + ".bias"))
             x = ctx["x"][i]
             wt = ctx["wts"][i]
-            # (the fused layer's BN-backward apply holds at most ops.APPLY_GMAX groups' coefficients,
-            # e.g. not 2 + 7 views)
-            lbs = (ops.cl_layer_bwd_slabs(self.act, N, ci, H, H, co, k, pad)
-                   if (self.LAYER_BWD and i > 0 and mode == 0 and wt[1] is not None and wt[3] is None
-                       and N // B <= ops.APPLY_GMAX and not self._mx_wgrad(i, N)) else 0)
+            lbs = self._layer_bwd_slabs(i, N, B, mode, wt)
             if lbs:
                 # the whole layer backward in one launch: dY formed in LDS from y and the pooled
                 # gradient, dX and the dW slabs from the same tiles (lbwd.hip); its own dX
@@ -576,7 +592,7 @@ class ConvBranch:
                 dx = ws.get("bwd_dx_lb", N * H * H * ci, self.act)
                 ops.mark(f"w{i}.begin")
                 ops.cl_layer_bwd(y, gout, st[2], st[3], coef, None, x, wt[1], dx, wparts, lbs, N, B, ci,
-                                 H, H, co, k, pad)
+                                 H, H, co, k, pad, codes=ctx["pool_codes"].get(i))
                 ops.sum_rows(wparts, lbs, co * ci * k * k, store.grad_of(ck + ".weight"))
                 ops.mark(f"w{i}.end")
                 gout = dx

@@ -565,6 +565,20 @@ def cl_bn_relu_pool(y, scale, shift, out, mode, N, B, C, H, W):
                         B, C, H, W, stream()))
 
 
+def cl_bn_relu_pool_codes(y, scale, shift, out, codes, N, B, C, H, W):
+    """cl_bn_relu_pool mode 0 (bf16) that also writes the backward's routing words: codes int32
+    [N][H/2][W/2][C/8], nibble e = 1 + first argmax of channel 8q + e where the max is > 0, else 0
+    (cl_layer_bwd's ``codes``).  codes None: no stores."""
+    npool = N * (H // 2) * (W // 2) * C
+    _need(y.dtype == out.dtype == torch.bfloat16 and y.numel() == N * H * W * C and out.numel() == npool,
+          "cl pool codes y / out")
+    _need(codes is None or (codes.dtype == torch.int32 and codes.numel() == npool // 8), "cl pool codes")
+    nb = (y.numel() + out.numel()) * 2 + (0 if codes is None else codes.numel() * 4)
+    _timed(f"cl_bn_relu_pool[{N}x{H}x{W}x{C} m0 {y.dtype} codes]", nb, 0,
+           lambda: call("avd_cl_bn_relu_pool_codes", p(y), p(scale), p(shift), p(out), p(codes), N, B,
+                        C, H, W, stream()))
+
+
 def cl_bn_bwd_rows(B, C, H, W, dtype):
     return lib.avd_cl_bn_bwd_rows(B, C, H, W, _DT[dtype])
 
@@ -633,10 +647,12 @@ def cl_layer_bwd_slabs(dtype, N, Cin, H, W, Cout, K, pad):
 
 
 def cl_layer_bwd(y, gout, scale, shift, coef, dy, x, wk_d, dx, parts, slabs, N, B, Cin, H, W, Cout,
-                 K, pad):
+                 K, pad, codes=None):
     """The whole backward of one conv layer in one launch (lbwd.hip): dY formed from y and the
     pooled gradient (or taken from ``dy`` when y is None) in LDS only, dX (bit-identical to
-    cl_conv_dgrad) and the weight-gradient slabs parts[slabs][Cout*Cin*K*K] (sum_rows)."""
+    cl_conv_dgrad) and the weight-gradient slabs parts[slabs][Cout*Cin*K*K] (sum_rows).
+    ``codes``: the forward's cl_bn_relu_pool_codes words of this y -- the gradient is routed by
+    them instead of a recomputed argmax (same dX and slabs; scale and shift are not read)."""
     Ho = H + 2 * pad - K + 1
     _need(slabs > 0 and parts.dtype == torch.float32 and parts.numel() >= slabs * Cout * Cin * K * K,
           "layer bwd slabs / parts")
@@ -648,12 +664,21 @@ def cl_layer_bwd(y, gout, scale, shift, coef, dy, x, wk_d, dx, parts, slabs, N, 
         _need(gout.dtype == torch.bfloat16 and gout.numel() == N * (Ho // 2) * (Ho // 2) * Cout, "layer bwd gout")
         _need(N % B == 0 and N // B <= APPLY_GMAX, "layer bwd groups")
         nb = (y.numel() + gout.numel() + x.numel() + dx.numel()) * 2
+        if codes is not None:
+            _need(codes.dtype == torch.int32 and codes.numel() == gout.numel() // 8, "layer bwd codes")
+            nb += codes.numel() * 4
     else:
         _need(dy is not None and dy.dtype == torch.bfloat16 and dy.numel() == N * Ho * Ho * Cout, "layer bwd dy")
         nb = (dy.numel() + x.numel() + dx.numel()) * 2
     nb += slabs * Cout * Cin * K * K * 4
     fl = 2 * 2 * N * Ho * Ho * Cout * Cin * K * K
-    _timed(f"cl_layer_bwd[{N}x{H}x{W}x{Cin}->{Cout} k{K} {'apply' if y is not None else 'dy'}]", nb, fl,
+    key = f"cl_layer_bwd[{N}x{H}x{W}x{Cin}->{Cout} k{K} {'apply' if y is not None else 'dy'}]"
+    if y is not None and codes is not None:
+        _timed(key, nb, fl,
+               lambda: call("avd_cl_layer_bwd_codes", p(y), p(gout), p(codes), p(coef), p(x), p(wk_d),
+                            p(dx), p(parts), int(slabs), 1, N, B, Cin, H, W, Cout, K, pad, stream()))
+        return
+    _timed(key, nb, fl,
            lambda: call("avd_cl_layer_bwd", p(y), p(gout), p(scale), p(shift), p(coef), p(dy), p(x),
                         p(wk_d), p(dx), p(parts), int(slabs), 1, N, B, Cin, H, W, Cout, K, pad, stream()))
 

@@ -99,7 +99,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void relu_pool_cl_kernel(
     const T* __restrict__ y, const float* __restrict__ scale, const float* __restrict__ shift,
     void* __restrict__ out, int mode, long long total, int B, int C, int H, int W, U32Div dcv,
-    U32Div dwp, U32Div dhp) {
+    U32Div dwp, U32Div dhp, unsigned* __restrict__ codes) {
   constexpr int V = Vec<T>::V;
   const int Hp = H / 2, Wp = W / 2, CV = C / V;
   // total < 2^32 (host-checked): 32-bit index decomposition by exact reciprocal multiplies
@@ -117,6 +117,17 @@ __global__ __launch_bounds__(256) void relu_pool_cl_kernel(
     load_win<T>(y, ((size_t)n * H + 2 * hp) * W + 2 * wp, W, C, c0, true, true, sc, sf, w);
     if (mode == 0) {
       Vec<T>::st(reinterpret_cast<T*>(out) + (size_t)pw * C + c0, w.mx);
+      if constexpr (V == 8) {
+        // the backward's routing, kept instead of recomputed (lbwd.hip AP = 2): nibble e =
+        // 1 + first argmax of channel c0 + e where the gradient passes (max > 0), else 0 --
+        // bwd_apply_cl_kernel's rule; one word per thread at its own index (coalesced)
+        if (codes) {
+          unsigned cw = 0u;
+#pragma unroll
+          for (int e = 0; e < V; ++e) cw |= (w.mx[e] > 0.f ? (unsigned)(w.arg[e] + 1) : 0u) << (4 * e);
+          codes[i] = cw;
+        }
+      }
     } else {   // mode 2: f32 (c, h, w) flatten
       float* o = reinterpret_cast<float*>(out) + (size_t)n * C * Hp * Wp + (size_t)hp * Wp + wp;
 #pragma unroll
@@ -529,9 +540,10 @@ int grid_for(long long total) {
 // ============================================================================= entry points
 int avd_cl_bn_relu_pool_impl(const void* y, int dt, const float* scale, const float* shift,
                              void* out, int mode, int N, int B, int C, int H, int W,
-                             hipStream_t st) {
+                             hipStream_t st, unsigned* codes) {
   const int V = dt == AVD_BF16 ? 8 : 4;
   if (C % V || N % B || H < 2 || W < 2) return AVD_ERR_SHAPE;
+  if (codes && (dt != AVD_BF16 || mode != 0)) return AVD_ERR_ARG;
   if (mode == 1) {
     const long long total = (long long)N * (C / V);
     if (dt == AVD_BF16)
@@ -547,11 +559,11 @@ int avd_cl_bn_relu_pool_impl(const void* y, int dt, const float* scale, const fl
     if (dt == AVD_BF16)
       relu_pool_cl_kernel<bf16><<<grid_for(total), 256, 0, st>>>((const bf16*)y, scale, shift, out,
                                                                  mode, total, B, C, H, W, dcv, dwp,
-                                                                 dhp);
+                                                                 dhp, codes);
     else
       relu_pool_cl_kernel<float><<<grid_for(total), 256, 0, st>>>((const float*)y, scale, shift, out,
                                                                   mode, total, B, C, H, W, dcv, dwp,
-                                                                  dhp);
+                                                                  dhp, nullptr);
   } else {
     return AVD_ERR_ARG;
   }

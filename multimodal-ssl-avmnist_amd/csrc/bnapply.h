@@ -27,6 +27,10 @@ struct ApplyArgs {
   int B;               // samples per BN group
   int G;               // groups (<= APPLY_GMAX)
   void* dy = nullptr;  // input-gradient kernel only: also store the dY it forms (tile interiors)
+  // the forward's routing words (avd_cl_bn_relu_pool_codes), [N][H/2][W/2][C/8]: nibble e of a
+  // word = 1 + argmax of channel 8q + e where the window's max is > 0, else 0.  With them the
+  // apply neither recomputes relu(bn(y)) nor reads scale / shift (apply_window_codes).
+  const unsigned* codes = nullptr;
 };
 constexpr int APPLY_GMAX = 8;
 
@@ -40,6 +44,15 @@ __device__ __forceinline__ void apply_load_ctab(float* ctab, const ApplyArgs& a,
   }
 }
 
+// ctab[g][3][C] = (k1, kx, k0): the code-routed apply's table
+template <int C>
+__device__ __forceinline__ void apply_load_ktab(float* ctab, const ApplyArgs& a, int tid, int nthr) {
+  for (int i = tid; i < a.G * 3 * C; i += nthr) {
+    const int g = i / (3 * C), r = i - g * 3 * C, k = r / C, c = r - k * C;
+    ctab[i] = a.coef[(g * C + c) * 3 + k];
+  }
+}
+
 typedef __attribute__((ext_vector_type(4))) unsigned u4a;
 
 // the prefetched inputs of one window task: 4 pixels x 8 channels of y, 8 pooled gradients
@@ -47,6 +60,41 @@ struct WinIn {
   u4a y[4];
   u4a g0, g1;   // gmode 0: g0 = 8 bf16; gmode 2: g0, g1 = 8 f32
 };
+
+// gmode 0 with the forward's routing word in g1.x: dy_k = bf16(k1 * (code == k + 1 ? g : 0) +
+// (kx * y_k + k0)) -- apply_window's two FMAs and rounding on the same operands, so the same dy
+// wherever the word is the forward's.  ct = ktab + g * 3 * C + c0 (rows k1, kx, k0, stride C).
+__device__ __forceinline__ void apply_window_codes(const WinIn& in, const float* ct, int C, u4a (&out)[4]) {
+  const unsigned yw[4][4] = {{in.y[0].x, in.y[0].y, in.y[0].z, in.y[0].w},
+                             {in.y[1].x, in.y[1].y, in.y[1].z, in.y[1].w},
+                             {in.y[2].x, in.y[2].y, in.y[2].z, in.y[2].w},
+                             {in.y[3].x, in.y[3].y, in.y[3].z, in.y[3].w}};
+  const unsigned gw[4] = {in.g0.x, in.g0.y, in.g0.z, in.g0.w};
+  const unsigned code = in.g1.x;
+  unsigned ow[4][4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float2 k1 = *reinterpret_cast<const float2*>(ct + 2 * e);
+    const float2 kx = *reinterpret_cast<const float2*>(ct + C + 2 * e);
+    const float2 k0 = *reinterpret_cast<const float2*>(ct + 2 * C + 2 * e);
+    float d[4][2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const unsigned nib = (code >> (8 * e + 4 * h)) & 15u;
+      const float gg = h ? __uint_as_float(gw[e] & 0xffff0000u) : __uint_as_float(gw[e] << 16);
+      const float a1 = h ? k1.y : k1.x, ax = h ? kx.y : kx.x, a0 = h ? k0.y : k0.x;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float yv = h ? __uint_as_float(yw[k][e] & 0xffff0000u) : __uint_as_float(yw[k][e] << 16);
+        d[k][h] = fmaf(a1, nib == (unsigned)(k + 1) ? gg : 0.f, fmaf(ax, yv, a0));
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ow[k][e] = pack_bf16x2(d[k][0], d[k][1]);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out[k] = u4a{ow[k][0], ow[k][1], ow[k][2], ow[k][3]};
+}
 
 __device__ __forceinline__ void apply_unpack8(u4a v, float (&f)[8]) {
   const unsigned w[4] = {v.x, v.y, v.z, v.w};

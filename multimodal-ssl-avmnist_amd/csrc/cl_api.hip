@@ -21,7 +21,7 @@ int avd_cl_conv_wgrad_impl(const void* x, const void* dy, int dt, float* parts, 
                            int H, int W, int Cout, int K, int pad, hipStream_t st);
 int avd_cl_bn_relu_pool_impl(const void* y, int dt, const float* scale, const float* shift,
                              void* out, int mode, int N, int B, int C, int H, int W,
-                             hipStream_t st);
+                             hipStream_t st, unsigned* codes = nullptr);
 int avd_cl_bn_bwd_rows_impl(int B, int C, int H, int W, int dt);
 int avd_cl_bn_bwd_reduce_impl(const void* y, int dt, const void* gout, int mode,
                               const float* scale, const float* shift, const float* mean,
@@ -314,6 +314,14 @@ int avd_cl_bn_relu_pool(const void* y, int dt, const float* scale, const float* 
   if (N <= 0 || B <= 0) return AVD_ERR_SHAPE;
   return avd_cl_bn_relu_pool_impl(y, dt, scale, shift, out, mode, N, B, C, H, W,
                                   avd_stream(stream));
+}
+
+int avd_cl_bn_relu_pool_codes(const void* y, const float* scale, const float* shift, void* out,
+                              unsigned* codes, int N, int B, int C, int H, int W, void* stream) {
+  if (!y || !scale || !shift || !out) return AVD_ERR_ARG;
+  if (N <= 0 || B <= 0) return AVD_ERR_SHAPE;
+  return avd_cl_bn_relu_pool_impl(y, AVD_BF16, scale, shift, out, 0, N, B, C, H, W,
+                                  avd_stream(stream), codes);
 }
 
 int avd_cl_bn_bwd_rows(int B, int C, int H, int W, int dt) {

@@ -12,7 +12,9 @@
 // persistent block walks TH-row tiles of its samples; per tile it
 //   * stages the dY tile with its 2-row / 2-column halo, formed in registers from y and the
 //     pooled gradient (AP = 1; one 2x2 window x 8 channels per task, bit-identical to
-//     bwd_apply_cl_kernel) or loaded from a dY tensor (AP = 0), and the X tile with its halo;
+//     bwd_apply_cl_kernel; AP = 2: the same dY with the gradient routed by the forward pool's
+//     code words, bn_cl.hip, instead of a recomputed relu(bn(y)) argmax -- half the apply's
+//     VALU work) or loaded from a dY tensor (AP = 0), and the X tile with its halo;
 //   * runs the input gradient on it exactly as conv_ws_kernel's DgrA2 does (weights resident in
 //     VGPRs, B fragments = one ds_read_b128 of the (tap, channel) k-group per pixel, same k
 //     order: bit-identical dX);
@@ -50,7 +52,7 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-template <int TH_, int OCC_, int PFD_ = 6, int GB_ = 1, int NCW_ = 1, int RP_ = 0>
+template <int TH_, int OCC_, int PFD_ = 6, int GB_ = 1, int NCW_ = 1, int RP_ = 0, int BAL_ = 0, int WGU_ = 0>
 struct Lb {
   static constexpr int CIN = 8, COUT = 16, K = 5, PAD = 2, H = 56, W = 56;   // the forward conv
   static constexpr int TH = TH_, TPS = H / TH, OCC = OCC_, PFD = PFD_, GB = GB_;
@@ -74,6 +76,17 @@ struct Lb {
   static constexpr int NCT = cdv(KK, 2), WKS = PIX / 32;
   static constexpr int NCW = NCW_, NW = cdv(NCT, NCW), NPW = 4 / NCW;
   static constexpr int WT = (ITH / 2) * (ITW / 2) * (COUT / 8);   // AP: window x channel-half tasks
+  // BAL (balanced apply staging): slot 0 = the tasks of the TH / 2 window rows a continuation
+  // tile forms anew (NEWT, spread over all four waves), slot 1 = the PAD window rows it copies
+  // from the previous tile (OLDT) -- a continuation tile runs slot 0 only.  Without BAL the
+  // tasks sit in linear order on the two slots, and in a continuation tile one wave has live
+  // lanes in both and runs the apply twice while the other three wait at the barrier.
+  static constexpr int BAL = BAL_;
+  static constexpr int NEWT = (TH / 2) * (ITW / 2) * (COUT / 8), OLDT = WT - NEWT;
+  static_assert(!BAL || (NEWT <= 256 && OLDT <= 256), "balanced staging: one slot each");
+  // WGU: the weight gradient's k-step loop unrolled, each k-step's pixel origin a constant
+  static constexpr int WGU = WGU_;
+  static_assert(!WGU || NPW == 1, "unrolled weight gradient: every wave walks all k-steps");
   static constexpr int DT = ITH * ITW * (COUT / 8);               // AP = 0: 16-byte dY tasks
   static constexpr int XT = ITH * ITW * (CIN / 8);                // 16-byte X tasks
   static constexpr int RED = (NPW - 1) * NCW * NW * 64;           // f4 slots: pixel partials
@@ -158,7 +171,9 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
                                                           float* __restrict__ parts, int ntiles,
                                                           ApplyArgs aa) {
   __shared__ __attribute__((aligned(16))) bf16 smem[L::SMEM];
-  __shared__ __attribute__((aligned(16))) float ctab[AP ? APPLY_GMAX * 5 * L::COUT : 4];
+  // AP = 1: (scale, shift, k1, kx, k0) per group; AP = 2 (code-routed): (k1, kx, k0) only
+  constexpr int CTR = AP == 1 ? 5 : 3;
+  __shared__ __attribute__((aligned(16))) float ctab[AP ? APPLY_GMAX * CTR * L::COUT : 4];
   // dY tile (row ty0 - PAD + r, column c - PAD) then the X tile (same origin), per buffer
   bf16* dys = smem;
   bf16* xs = smem + L::DY_ELEMS;
@@ -216,18 +231,23 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
   constexpr int HP = L::H / 2, WP = L::W / 2;
   constexpr int YT = AP ? L::WT : L::DT;
   constexpr int YSL = cdv(YT, 256), XSL = cdv(L::XT, 256);
+  constexpr bool BAL = AP && L::BAL;
+  static_assert(!BAL || YSL == 2, "balanced staging: two slots");
+  // slot i's task of this thread, whether it exists, and whether a continuation tile skips it
+  auto ytask = [&](int i) { return BAL ? (i == 0 ? tid + L::OLDT : tid) : tid + 256 * i; };
+  auto yhas = [&](int i) { return BAL ? (i == 0 ? tid < L::NEWT : tid < L::OLDT) : tid + 256 * i < YT; };
   int ygo[YSL], ylo[YSL], yrow[YSL], ygg[YSL];
   int xgo[XSL], xlo[XSL], xrow[XSL];
 #pragma unroll
   for (int i = 0; i < YSL; ++i) {
-    const int task = tid + 256 * i;
+    const int task = ytask(i);
     const int q = task & 1, w = task >> 1;             // COUT / 8 = 2 channel halves
     if constexpr (AP) {
       const int wc2 = w % (L::ITW / 2), wr = w / (L::ITW / 2);
       const int r = 2 * wr, c = 2 * wc2, ix = c - L::PAD;
       yrow[i] = r;
       ylo[i] = (r * L::RS + c) * L::PS + 8 * q;
-      ygo[i] = (task < YT && ix >= 0 && ix < L::W) ? (r * L::W + ix) * L::COUT + 8 * q : -1;
+      ygo[i] = (yhas(i) && ix >= 0 && ix < L::W) ? (r * L::W + ix) * L::COUT + 8 * q : -1;
       ygg[i] = (wr * WP + ix / 2) * L::COUT + 8 * q;
     } else {
       const int c = w % L::ITW, r = w / L::ITW, ix = c - L::PAD;
@@ -245,7 +265,8 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
     xlo[i] = (r * L::XW + c) * L::XS;
     xgo[i] = (task < L::XT && ix >= 0 && ix < L::W) ? (r * L::W + ix) * L::CIN : -1;
   }
-  if constexpr (AP) apply_load_ctab<L::COUT>(ctab, aa, tid, 256);
+  if constexpr (AP == 1) apply_load_ctab<L::COUT>(ctab, aa, tid, 256);
+  if constexpr (AP == 2) apply_load_ktab<L::COUT>(ctab, aa, tid, 256);
 
   WinIn wpre[AP ? YSL : 1];
   u4 ypre[AP ? 1 : YSL];
@@ -261,6 +282,7 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
     const bf16* bx = x + row0 * L::W * L::CIN;
 #pragma unroll
     for (int i = 0; i < YSL; ++i) {
+      if (BAL && i == 1 && cont) continue;     // (block-uniform) the copied rows' slot
       const bool ok = ygo[i] >= 0 && (unsigned)(ty0 - L::PAD + yrow[i]) < (unsigned)L::H &&
                       !(cont && yrow[i] < RR);
       const bf16* p = by + (ok ? ygo[i] : 0);
@@ -271,6 +293,11 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
         wpre[i].y[3] = ldg16(ok ? (const void*)(p + (L::W + 1) * L::COUT) : &kZeroL);
         const bf16* gb = reinterpret_cast<const bf16*>(aa.gout) + ((long long)n * HP + (ty0 - L::PAD) / 2) * WP * L::COUT;
         wpre[i].g0 = ldg16(ok ? (const void*)(gb + ygg[i]) : &kZeroL);
+        if constexpr (AP == 2) {
+          // the forward's routing word of this (pooled pixel, channel octet): gout's index / 8
+          const unsigned* cb = aa.codes + ((long long)n * HP + (ty0 - L::PAD) / 2) * WP * (L::COUT / 8);
+          wpre[i].g1.x = ok ? __builtin_nontemporal_load(cb + (ygg[i] >> 3)) : 0u;
+        }
       } else {
         ypre[i] = ldg16(ok ? (const void*)p : &kZeroL);
       }
@@ -296,12 +323,16 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
     }
 #pragma unroll
     for (int i = 0; i < YSL; ++i) {
-      const int task = tid + 256 * i;
-      if (task >= YT || (cont && yrow[i] < RR)) continue;
+      if (BAL && i == 1 && cont) continue;
+      const int task = ytask(i);
+      if (!yhas(i) || (cont && yrow[i] < RR)) continue;
       if constexpr (AP) {
         u4 o[4] = {u4{0u, 0u, 0u, 0u}, u4{0u, 0u, 0u, 0u}, u4{0u, 0u, 0u, 0u}, u4{0u, 0u, 0u, 0u}};
-        if (ygo[i] >= 0 && (unsigned)(ty0 - L::PAD + yrow[i]) < (unsigned)L::H)
-          apply_window_lean(wpre[i], ctab + (n / aa.B) * 5 * L::COUT + 8 * (task & 1), L::COUT, o);
+        if (ygo[i] >= 0 && (unsigned)(ty0 - L::PAD + yrow[i]) < (unsigned)L::H) {
+          const float* ct = ctab + (n / aa.B) * CTR * L::COUT + 8 * (task & 1);
+          if constexpr (AP == 2) apply_window_codes(wpre[i], ct, L::COUT, o);
+          else apply_window_lean(wpre[i], ct, L::COUT, o);
+        }
         *reinterpret_cast<u4*>(dys + ylo[i]) = o[0];
         *reinterpret_cast<u4*>(dys + ylo[i] + L::PS) = o[1];
         *reinterpret_cast<u4*>(dys + ylo[i] + L::RS * L::PS) = o[2];
@@ -393,8 +424,48 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
       bb[j][1] = tr4(xs + xb[1] + xo[j]);
     }
   };
+  // WGU: k-step KS starts at the constant pixel 32 KS = (row r0, column c0); the lane's pixel
+  // is kp < 32 further on, so its row is r0 or -- only where c0 + 31 >= W, and then for the
+  // lanes with kp >= W - c0 -- r0 + 1.  The constant part of both offsets folds into the
+  // ds_read offset fields; same pixels, fragments and MFMA order as wg_load.
+  const int kp0 = kpix(g, 0, q4);                       // h = 1: kp0 + 8
+  const int lpa = kp0 * L::PS + 4 * p4;
+  int lxo[L::NW];
+#pragma unroll
+  for (int j = 0; j < L::NW; ++j) lxo[j] = kp0 * L::XS + xo[j];
+  auto wg_load_c = [&](auto ksc, u2 (&af)[2], u2 (&bb)[L::NW][2]) {
+    constexpr int P0 = 32 * decltype(ksc)::value, r0 = P0 / L::W, c0 = P0 % L::W;
+    constexpr int cpa = ((r0 + L::PAD) * L::RS + c0 + L::PAD) * L::PS, cxb = (r0 * L::XW + c0) * L::XS;
+    constexpr int wpa = (L::RS - L::W) * L::PS, wxb = (L::XW - L::W) * L::XS;   // one row on
+    static_for<0, 2>([&](auto hc) {
+      constexpr int h = decltype(hc)::value;
+      int pa = lpa, xw = 0;
+      if constexpr (c0 + 8 * h + 23 >= L::W) {          // kp0 <= 23
+        const bool wr = kp0 + 8 * h >= L::W - c0;
+        pa += wr ? wpa : 0;
+        xw = wr ? wxb : 0;
+      }
+      af[h] = tr4(dys + pa + (cpa + 8 * h * L::PS));
+#pragma unroll
+      for (int j = 0; j < L::NW; ++j) bb[j][h] = tr4(xs + (lxo[j] + xw) + (cxb + 8 * h * L::XS));
+    });
+  };
   // the tile's interior pixel P (row P / W, column P % W) sits at dY tile row + PAD, column + PAD
   auto wgrad_tile = [&]() {
+    if constexpr (L::WGU) {
+      u2 af[2][2], bb[2][L::NW][2];
+      wg_load_c(IC<0>{}, af[0], bb[0]);
+      static_for<0, L::WKS>([&](auto kc) {
+        constexpr int ks = decltype(kc)::value, c = ks & 1;
+        if constexpr (ks + 1 < L::WKS) wg_load_c(IC<ks + 1>{}, af[c ^ 1], bb[c ^ 1]);
+        __builtin_amdgcn_sched_barrier(0);
+        const bf16x8 a8 = frag8(af[c][0], af[c][1]);
+#pragma unroll
+        for (int j = 0; j < L::NW; ++j) wacc[j] = mma(a8, frag8(bb[c][j][0], bb[c][j][1]), wacc[j]);
+        __builtin_amdgcn_sched_barrier(0);
+      });
+      return;
+    }
     int ks = wq;
     if (ks >= L::WKS) return;
     u2 af[2][2], bb[2][L::NW][2];
@@ -471,13 +542,26 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
   for (int e = tid; e < L::COUT * PER_CO / 4; e += 256) o4[e] = t4[e];
 }
 
-//          TH OCC PFD GB NCW RP
-typedef Lb<8, 2, 3, 1, 4, 1> LbA2;
+// LBWD_BAL, LBWD_WGU (build-time, for A/B builds): 0 = the apply tasks in linear order on the
+// two slots / the rolled weight-gradient loop with its per-k-step divisions
+#ifndef LBWD_BAL
+#define LBWD_BAL 1
+#endif
+#ifndef LBWD_WGU
+#define LBWD_WGU 1
+#endif
+//          TH OCC PFD GB NCW RP BAL       WGU
+typedef Lb<8, 2, 3, 1, 4, 1, LBWD_BAL, LBWD_WGU> LbA2;
 
 int lb_occ_ap() {
   static int occ = 0;
   if (!occ) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, lbwd_kernel<LbA2, 1>, 256, 0) != hipSuccess || occ <= 0)
+    // the least of the two apply variants, so one slab count serves both
+    int o1 = 0, o2 = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o1, lbwd_kernel<LbA2, 1>, 256, 0) == hipSuccess &&
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&o2, lbwd_kernel<LbA2, 2>, 256, 0) == hipSuccess)
+      occ = std::min(o1, o2);
+    if (occ <= 0)
       occ = 1;
   }
   return occ;
@@ -507,17 +591,18 @@ int avd_cl_layer_bwd_slabs(int dt, int N, int Cin, int H, int W, int Cout, int K
   return std::max(1, grid_cap(std::min(ntiles, lb_cus() * lb_occ_ap())));
 }
 
-int avd_cl_layer_bwd(const void* y, const void* gout, const float* scale, const float* shift,
-                     const float* coef, const void* dy, const void* x, const void* wk_d, void* dx,
-                     float* parts, int slabs, int dt, int N, int B, int Cin, int H, int W, int Cout,
-                     int K, int pad, void* stream) {
+namespace {
+int lbwd_launch(const void* y, const void* gout, const float* scale, const float* shift,
+                const unsigned* codes, const float* coef, const void* dy, const void* x,
+                const void* wk_d, void* dx, float* parts, int slabs, int dt, int N, int B, int Cin,
+                int H, int W, int Cout, int K, int pad, void* stream) {
   if (!lb_serves(dt, N, Cin, H, W, Cout, K, pad)) {
     avd_set_error(hipErrorInvalidValue);
     return AVD_ERR_SHAPE;
   }
   if (!x || !wk_d || !dx || !parts) return AVD_ERR_ARG;
   const bool ap = y != nullptr;
-  if (ap ? (!gout || !scale || !shift || !coef) : !dy) return AVD_ERR_ARG;
+  if (ap ? (!gout || !coef || (codes ? false : (!scale || !shift))) : !dy) return AVD_ERR_ARG;
   if (ap && (B <= 0 || N % B || N / B > APPLY_GMAX)) return AVD_ERR_SHAPE;
   const int ntiles = N * LbA2::TPS;
   // the caller's slab count (the parts buffer it sized) is the grid: no re-derivation here
@@ -525,8 +610,12 @@ int avd_cl_layer_bwd(const void* y, const void* gout, const float* scale, const 
   ApplyArgs aa{};
   aa.gout = gout; aa.scale = scale; aa.shift = shift; aa.coef = coef;
   aa.B = ap ? B : N; aa.G = ap ? N / B : 1;
+  aa.codes = codes;
   hipStream_t st = avd_stream(stream);
-  if (ap)
+  if (ap && codes)
+    lbwd_kernel<LbA2, 2><<<slabs, 256, 0, st>>>((const bf16*)y, (const bf16*)x, (const bf16*)wk_d, (bf16*)dx,
+                                                 parts, ntiles, aa);
+  else if (ap)
     lbwd_kernel<LbA2, 1><<<slabs, 256, 0, st>>>((const bf16*)y, (const bf16*)x, (const bf16*)wk_d, (bf16*)dx,
                                                  parts, ntiles, aa);
   else
@@ -534,4 +623,21 @@ int avd_cl_layer_bwd(const void* y, const void* gout, const float* scale, const 
                                                  parts, ntiles, aa);
   AVD_CHECK_LAUNCH();
   return AVD_OK;
+}
+}  // namespace
+
+int avd_cl_layer_bwd(const void* y, const void* gout, const float* scale, const float* shift,
+                     const float* coef, const void* dy, const void* x, const void* wk_d, void* dx,
+                     float* parts, int slabs, int dt, int N, int B, int Cin, int H, int W, int Cout,
+                     int K, int pad, void* stream) {
+  return lbwd_launch(y, gout, scale, shift, nullptr, coef, dy, x, wk_d, dx, parts, slabs, dt, N, B,
+                     Cin, H, W, Cout, K, pad, stream);
+}
+
+int avd_cl_layer_bwd_codes(const void* y, const void* gout, const unsigned* codes, const float* coef,
+                           const void* x, const void* wk_d, void* dx, float* parts, int slabs, int dt,
+                           int N, int B, int Cin, int H, int W, int Cout, int K, int pad, void* stream) {
+  if (!y || !codes) return AVD_ERR_ARG;
+  return lbwd_launch(y, gout, nullptr, nullptr, codes, coef, nullptr, x, wk_d, dx, parts, slabs, dt,
+                     N, B, Cin, H, W, Cout, K, pad, stream);
 }

@@ -1,6 +1,7 @@
 """The fused 56² layer backward alone at config-2 size, with the BN-backward apply in the kernel
-(y + pooled gradient, AP = 1) and with a precomputed dY (AP = 0): how much of the launch is the
-apply.    python tools/lbwd_ap.py"""
+recomputing the pool's argmax (y + pooled gradient, AP = 1), routed by the forward pool's codes
+(AP = 2), and with a precomputed dY (AP = 0): how much of the launch is the apply; and the
+forward pool with and without the code stores.    python tools/lbwd_ap.py"""
 import os
 import sys
 
@@ -32,8 +33,15 @@ def main():
     slabs = ops.cl_layer_bwd_slabs(bf, N, Cin, H, H, Cout, K, pad)
     parts = torch.empty(slabs * Cout * Cin * K * K, device="cuda")
     dx = torch.empty_like(x)
+    pooled = torch.empty_like(gout)
+    codes = torch.empty(gout.numel() // 8, dtype=torch.int32, device="cuda")
+    ops.cl_bn_relu_pool_codes(y, scale, shift, pooled, codes, N, B, Cout, H, H)
     runs = {"apply (AP=1)": lambda: ops.cl_layer_bwd(y, gout, scale, shift, coef, None, x, wk, dx, parts, slabs,
                                                      N, B, Cin, H, H, Cout, K, pad),
+            "apply from codes (AP=2)": lambda: ops.cl_layer_bwd(y, gout, scale, shift, coef, None, x, wk, dx, parts,
+                                                                slabs, N, B, Cin, H, H, Cout, K, pad, codes=codes),
+            "pool": lambda: ops.cl_bn_relu_pool(y, scale, shift, pooled, 0, N, B, Cout, H, H),
+            "pool + codes": lambda: ops.cl_bn_relu_pool_codes(y, scale, shift, pooled, codes, N, B, Cout, H, H),
             "dY given (AP=0)": lambda: ops.cl_layer_bwd(None, None, None, None, None, dy, x, wk, dx, parts, slabs,
                                                         N, B, Cin, H, H, Cout, K, pad)}
     for name, fn in runs.items():
