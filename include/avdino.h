@@ -662,6 +662,20 @@ int avd_bn_eval_coef(const float* gamma, const float* beta, const float* running
                      const float* running_var, float eps, int C, float* scale, float* shift,
                      void* stream);
 
+/* An eval-mode 3x3 layer in one launch (conv3.hip): conv (pad 1, + bias) -> BatchNorm as the
+ * fixed per-channel affine (scale, shift) [O] of avd_bn_eval_coef -> ReLU -> 2x2 max-pool over
+ * NHWC bf16 x [N][H][W][C], wk the avd_cl_weight_layout rows; the conv output never reaches
+ * memory.  mode 0: out = pooled map, bf16 NHWC [N][H/2][W/2][O]; mode 1: out = global average
+ * of the pooled map, f32 [N][O].  Bit-identical to avd_cl_conv_fwd (stats = NULL) followed by
+ * avd_cl_bn_relu_pool in the same mode.  Any N (no batch-divisibility rule).
+ * avd_c3_eval_serves: 1 if served (C % 32 == 0, O % 32 == 0, O <= 256, W <= 62; mode 1 needs
+ * maps that fit a tile whole), else 0.  avd_c3_conv_eval: 1 = launched, 0 = not served (the
+ * caller keeps the two launches), < 0 = error. */
+int avd_c3_eval_serves(int N, int H, int W, int C, int O, int mode);
+int avd_c3_conv_eval(const void* x, const void* wk, const float* bias, const float* scale,
+                     const float* shift, void* out, int mode, int N, int H, int W, int C, int O,
+                     void* stream);
+
 /* y += a*x over n floats (16-byte aligned): folds a scattered gradient slab into the local one
  * (global-negative contrastive losses, avdino/contrastive.py). */
 int avd_axpy(float* y, const float* x, long long n, float a, void* stream);

@@ -102,6 +102,8 @@ PROTOS = {
     "avd_adamw": [P, P, P, P, L, F, F, F, F, F, F, F, P],
     "avd_axpy": [P, P, L, F, P],
     "avd_bn_eval_coef": [P, P, P, P, F, I, P, P, P],
+    "avd_c3_eval_serves": [I, I, I, I, I, I],
+    "avd_c3_conv_eval": [P, P, P, P, P, P, I, I, I, I, I, I, P],
     "avd_argmax_correct": [P, L, I, I, P, P, P],
     "avd_sum": [P, I, F, P, P],
     "avd_stage_views": [P, I, P, I, P, I, I, P, I, P],

@@ -1,4 +1,5 @@
-"""Downstream evaluation of a trained DINO student: the reference's
+"""Downstream evaluation of a trained DINO student or, with
+``is_dino_based=False``, of a trained SimCLR model's towers and their late fusion: the reference's
 ``training_structures/dino_train.py`` functions and ``models/dino.py``'s downstream modules,
 on libavdino kernels with every tensor on the device.
 
@@ -15,8 +16,9 @@ on libavdino kernels with every tensor on the device.
   compute_classification_metrics dino_train.py:47-102
   compute_accuracies            run_dino.py:481-501
 
-Semantics kept from the reference: the encoder is a deep copy of ``pretrained.student`` (the
-trained model is never touched); the classifier's training epochs run the copy in TRAIN mode
+Semantics kept from the reference: the encoder is a deep copy of ``pretrained.student`` -- of the
+encoder itself for ``is_dino_based=False``, where ``modality`` selects its input and a fusion
+encoder takes both -- so the trained model is never touched; the classifier's training epochs run the copy in TRAIN mode
 (``model.train()`` reaches the copy: batch-stat BatchNorm whose running statistics update the
 copy, fusion dropout active) and evaluation in EVAL mode; the best epoch is the first with the
 highest validation accuracy (strict ``>``), and its classifier AND the copy's running
@@ -39,10 +41,24 @@ from .trainer import cosine_lr
 
 
 def _source(pretrained_model, is_dino_based=True):
-    """(ParamStore, kind, D, E, act dtype, fusion dropout) of a DINO model's student."""
+    """(ParamStore, kind, D, E, act dtype, fusion dropout) of a DINO model's student, or
+    (``is_dino_based=False``, models/dino.py:1769, 1821) of the encoder itself: a tower handle of
+    a trained SimCLR model (``model.image_encoder`` / ``model.audio_encoder``; kind = its
+    UNI_ENCODERS kind) or a LateFusionEncoder over two of them (kind = "late_fusion_<fusion>",
+    D = the fused width)."""
     if not is_dino_based:
-        raise NotImplementedError("downstream evaluation of non-DINO encoders (SimCLR / InfoNCE "
-                                  "notebooks) is outside the MI355X hot path")
+        enc = pretrained_model
+        if hasattr(enc, "fusion") and hasattr(enc, "image_encoder") and hasattr(enc, "audio_encoder"):
+            if enc.image_encoder.store is not enc.audio_encoder.store:
+                raise NotImplementedError("late fusion of towers from two different models")
+            if enc.image_encoder.act_dtype != enc.audio_encoder.act_dtype:
+                raise ValueError("late fusion towers run in different activation dtypes")
+            return (enc.image_encoder.store, f"late_fusion_{enc.fusion}", enc.output_dim, None,
+                    enc.image_encoder.act_dtype, 0.0)
+        if not all(hasattr(enc, a) for a in ("store", "kind", "prefix", "output_dim", "act_dtype")):
+            raise TypeError("is_dino_based=False takes a SimCLR tower (model.image_encoder / "
+                            "model.audio_encoder) or a LateFusionEncoder over two of them")
+        return enc.store, enc.kind, enc.output_dim, None, enc.act_dtype, 0.0
     m = pretrained_model.model if hasattr(pretrained_model, "configure_optimizers") else pretrained_model
     enc = m.student_spec
     kind = getattr(enc, "kind", None) or enc.arch
@@ -50,6 +66,19 @@ def _source(pretrained_model, is_dino_based=True):
         else torch.float32
     return (m.store, kind, m.output_dim, getattr(m, "encoder_output_dim", None), act,
             getattr(m.hp, "fusion_dropout", 0.3))
+
+
+def _probe_kwargs(pretrained_model, is_dino_based):
+    """LinearProbe's encoder selection for ``_source``'s model: the key prefix of a SimCLR tower,
+    or the two towers (image first, as the reference concatenates) of a late-fusion encoder."""
+    if is_dino_based:
+        return {}
+    enc = pretrained_model
+    if hasattr(enc, "fusion"):
+        return {"towers": [(enc.image_encoder.kind, enc.image_encoder.prefix),
+                           (enc.audio_encoder.kind, enc.audio_encoder.prefix)],
+                "fusion": enc.fusion}
+    return {"prefix": enc.prefix}
 
 
 def _as_batch(batch, device):
@@ -65,7 +94,8 @@ class FeatureExtractor(nn.Module):
     def __init__(self, pretrained_model, is_dino_based=True):
         super().__init__()
         store, kind, D, E, act, fd = _source(pretrained_model, is_dino_based)
-        self.probe = LinearProbe(store, kind, D, E, act_dtype=act, fusion_dropout=fd)
+        self.probe = LinearProbe(store, kind, D, E, act_dtype=act, fusion_dropout=fd,
+                                 **_probe_kwargs(pretrained_model, is_dino_based))
         self.output_dim = D
         self.modality = getattr(self.probe, "modality", None)
         self.is_unimodal = self.modality is not None
@@ -91,7 +121,8 @@ class DownstreamClassifier(nn.Module):
             raise NotImplementedError("AVMNIST has 10 classes")
         store, kind, D, E, act, fd = _source(pretrained_model, is_dino_based)
         self.probe = LinearProbe(store, kind, D, E, lr=lr, weight_decay=weight_decay, act_dtype=act,
-                                 fusion_dropout=fd, seed=seed, classifier_state=classifier_state)
+                                 fusion_dropout=fd, seed=seed, classifier_state=classifier_state,
+                                 **_probe_kwargs(pretrained_model, is_dino_based))
         self.output_dim = D
         self.modality = getattr(self.probe, "modality", None)
         self.is_unimodal = self.modality is not None

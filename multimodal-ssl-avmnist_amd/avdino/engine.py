@@ -294,8 +294,7 @@ class ConvBranch:
         nl = len(self.stack.convs)
         for i, (ci, co, k, pad) in enumerate(self.stack.convs):
             H, Ho, Hp = self.dims[i]
-            y = ws.get(f"{tag}.y{i}", N * Ho * Ho * co, self.act)
-            self._conv_fwd(i, h, wts[i], store[self.stack.conv_keys[i] + ".bias"], y, None, N, N)
+            bias = store[self.stack.conv_keys[i] + ".bias"]
             bk = self.stack.bn_keys[i]
             coef = ws.get(f"{tag}.ev{i}", 2 * co).view(2, co)
             ops.bn_eval_coef(store[bk + ".weight"], store[bk + ".bias"], store[bk + ".running_mean"],
@@ -306,9 +305,35 @@ class ConvBranch:
             else:
                 mode = 0
                 out = ws.get(f"{tag}.x{i + 1}", N * Hp * Hp * co, self.act)
+            h, x_in = out, h
+            if self._eval_fused(i, x_in, wts[i], bias, coef, out, mode, N):
+                continue
+            y = ws.get(f"{tag}.y{i}", N * Ho * Ho * co, self.act)
+            self._conv_fwd(i, x_in, wts[i], bias, y, None, N, N)
             ops.cl_bn_relu_pool(y, coef[0], coef[1], out, mode, N, N, co, Ho, Ho)
-            h = out
         return h.view(N, -1)
+
+    # eval-mode layers without a stored conv output (bit-identical to the two launches): the
+    # 3x3 layers i > 0 as one launch (avd_c3_conv_eval: conv + BN affine + ReLU + pool [+ GAP]),
+    # the first layer through the recompute apply pass (BN coefficients = one group)
+    EVAL_FUSED = True
+
+    def _eval_fused(self, i, x, wt, bias, coef, out, mode, N):
+        """Launch layer i's fused eval forward into ``out``; False: not served, nothing launched."""
+        if not (self.EVAL_FUSED and self.act == torch.bfloat16 and wt[0] is not None):
+            return False
+        ci, co, k, pad = self.stack.convs[i]
+        H = self.dims[i][0]
+        if i == 0:
+            if not (mode == 0 and ops.cl_c1_recompute_rows(ops.C1_APPLY, self.act, N, N, ci, H, H,
+                                                           co, k, pad) > 0):
+                return False
+            ops.cl_c1_recompute(ops.C1_APPLY, x, wt[0], bias, N, N, ci, H, H, co, k, pad,
+                                scale=coef[0], shift=coef[1], z=out)
+            return True
+        if not (k == 3 and pad == 1 and mode in (0, 1) and ops.c3_eval_serves(N, H, H, ci, co, mode)):
+            return False
+        return ops.c3_conv_eval(x, wt[0], bias, coef[0], coef[1], out, mode, N, H, H, ci, co)
 
     # ---- first layer without a stored conv output (avd_cl_c1_recompute).  The route switches
     # below are plain class attributes (tests flip them to compare routes; nothing reads the

@@ -324,6 +324,25 @@ class _StudentView:
         return iter(self.owner.trainable_arenas())
 
 
+class _EncoderHandle:
+    """One tower of a trained MultiModalSimCLRModel as the reference exposes it
+    (multimodal_simclr.py:12-20 ``image_encoder`` / ``audio_encoder``): ``output_dim`` and
+    ``modality`` for the downstream code, plus what the engine needs to run it -- the
+    UNI_ENCODERS ``kind``, the state-dict key ``prefix`` and the activation dtype.  A light view:
+    the weights stay in the owner's ParamStore (``store``), nothing is copied."""
+
+    def __init__(self, owner, kind, prefix, output_dim, modality, act_dtype):
+        self.owner, self.kind, self.prefix = owner, kind, prefix
+        self.output_dim, self.modality, self.act_dtype = output_dim, modality, act_dtype
+
+    @property
+    def store(self):
+        return self.owner.store
+
+    def parameters(self):
+        return iter(self.owner.trainable_arenas())
+
+
 class MultiModalDINO(_ArenaModule):
     """Student/teacher multimodal DINO (models/dino.py:588-727) on the HIP engine."""
 
@@ -626,6 +645,9 @@ class _LightningShaped(_LightningBase):
             v = value.detach() if torch.is_tensor(value) else value
             self.logged[name] = v
             self.logged_history.setdefault(name, []).append(v)
+
+        def on_train_epoch_end(self):
+            """LightningModule's hook (a no-op unless a module overrides it); the Trainer calls it."""
 
     def forward(self, batch):
         return self.model(batch)
@@ -998,6 +1020,12 @@ class MultiModalSimCLRModel(_ArenaModule):
         self._ranges = tuple(store.group_range(i) for i in range(2))
         self._bind(store, [("arena_image",) + self._ranges[0], ("arena_audio",) + self._ranges[1]])
         self.hp = Hyper(weight_decay=0.0)
+        self.precision = precision
+        act = _DT[precision]
+        self.image_encoder = _EncoderHandle(self, "image_simple", "image_encoder", output_dim,
+                                            "image", act)
+        self.audio_encoder = _EncoderHandle(self, "spectrogram_simple", "audio_encoder", output_dim,
+                                            "audio", act)
         self.engine = None
         if self.device.type == "cuda":
             self.engine = SimCLREngine(store, output_dim, projection_dim, self.hp,

@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from ._lib import BF16, F32, call, lib
+from ._lib import BF16, F32, call, check, lib
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
 
@@ -1091,6 +1091,34 @@ def bn_eval_coef(gamma, beta, rm, rv, scale, shift, eps=1e-5):
     C = gamma.numel()
     _need(all(t.numel() >= C for t in (beta, rm, rv, scale, shift)), "bn eval coef")
     call("avd_bn_eval_coef", p(gamma), p(beta), p(rm), p(rv), eps, C, p(scale), p(shift), stream())
+
+
+def c3_eval_serves(N, H, W, C, O, mode):
+    """The fused eval-mode 3x3 layer (avd_c3_conv_eval) serves this bf16 shape."""
+    return lib.avd_c3_eval_serves(N, H, W, C, O, mode) > 0
+
+
+def c3_conv_eval(x, wk, bias, scale, shift, out, mode, N, H, W, C, O):
+    """conv3x3 (pad 1, + bias) -> eval BatchNorm (scale, shift [O]) -> ReLU -> 2x2 max-pool in one
+    launch, bf16 NHWC; mode 0: pooled map [N, H/2, W/2, O] bf16; mode 1: its global average f32
+    [N, O].  Bit-identical to cl_conv_fwd (no stats) + cl_bn_relu_pool.  Returns False when the
+    shape is not served (nothing launched: the caller keeps the two launches)."""
+    _need(mode in (0, 1), "c3 eval mode")
+    _need(x.dtype == wk.dtype == torch.bfloat16 and x.numel() == N * H * W * C, "c3 eval x")
+    _need(wk.numel() >= cl_weight_elems(O, C, 3, 0), "c3 eval wk")
+    _need((bias is None or bias.numel() >= O) and scale.numel() >= O and shift.numel() >= O and
+          scale.dtype == shift.dtype == torch.float32, "c3 eval coefficients")
+    want = N * (H // 2) * (W // 2) * O if mode == 0 else N * O
+    _need(out.numel() == want and out.dtype == (torch.bfloat16 if mode == 0 else torch.float32),
+          "c3 eval out")
+    nb = x.numel() * 2 + out.numel() * out.element_size() + 9 * C * O * 2
+    fl = 2 * N * O * H * W * C * 9
+    rc = _timed(f"c3_conv_eval[{N}x{H}x{W}x{C}->{O} m{mode}]", nb, fl,
+                lambda: lib.avd_c3_conv_eval(p(x), p(wk), p(bias), p(scale), p(shift), p(out), mode,
+                                             N, H, W, C, O, stream()))
+    if rc < 0:
+        check(rc, "avd_c3_conv_eval")
+    return rc == 1
 
 
 def argmax_correct(logits, ld, R, C, targets, correct):

@@ -75,8 +75,11 @@ class _MultiEncoder:
 
 
 class _UniEncoder:
-    def __init__(self, kind, act, gm):
-        self.enc = UniEncoder(kind, "student", act, gm)
+    """One UNI_ENCODERS network under the state-dict prefix ``prefix``: a DINO model's
+    ``student``, or a SimCLR tower (``image_encoder`` / ``audio_encoder``, spec.simclr_sd)."""
+
+    def __init__(self, kind, act, gm, prefix="student"):
+        self.enc = UniEncoder(kind, prefix, act, gm)
 
     def __call__(self, ws, st, x, N, train):
         if train:
@@ -84,6 +87,60 @@ class _UniEncoder:
             st.flush_nbt()
             return out
         return self.enc.forward_eval(ws, st, "pu", x, N)
+
+
+FUSIONS = ("concat", "sum", "mean")
+
+
+class _TwoTower:
+    """Late fusion of an image and an audio tower of one store (the reference's
+    LateFusionEncoder.forward, ssl_train.py:277-292, without gradients): both towers, then
+    cat([z_image, z_audio], 1), z_image + z_audio or (z_image + z_audio) / 2.  For concat each
+    tower's last Linear writes its half of the fused row directly."""
+
+    def __init__(self, towers, fusion, act, gm):
+        (ki, pi), (ka, pa) = towers
+        self.img, self.aud = UniEncoder(ki, pi, act, gm), UniEncoder(ka, pa, act, gm)
+        if (self.img.modality, self.aud.modality) != ("image", "audio"):
+            raise ValueError("late fusion takes an image tower and an audio tower")
+        if fusion not in FUSIONS:
+            raise ValueError(f"Unknown fusion strategy: {fusion}")
+        self.fusion = fusion
+
+    @staticmethod
+    def _tower(enc, ws, st, tag, x, N, train, out=None, out_ld=None, out_off=0):
+        if train:
+            h, _ = enc.branch.forward(ws, st, tag, x, N, 1, True, False)
+        else:
+            h = enc.branch.forward_eval(ws, st, tag, x, N)
+        for i, k in enumerate(enc.lins):
+            w = st[k + ".weight"]
+            if i == len(enc.lins) - 1 and out is not None:
+                ops.linear_fwd(h, w, st[k + ".bias"], out, N, out_ld=out_ld, out_off=out_off, mode=enc.gm)
+                return out
+            o = ws.get(f"{tag}.lin{i}", N * w.shape[0])
+            ops.linear_fwd(h, w, st[k + ".bias"], o, N, mode=enc.gm)
+            h = o
+        return h
+
+    def __call__(self, ws, st, x_img, x_aud, N, train):
+        Di = st[self.img.lins[-1] + ".weight"].shape[0]
+        Da = st[self.aud.lins[-1] + ".weight"].shape[0]
+        if self.fusion == "concat":
+            out = ws.get("p.fused", N * (Di + Da))
+            self._tower(self.img, ws, st, "pui", x_img, N, train, out, Di + Da, 0)
+            self._tower(self.aud, ws, st, "pua", x_aud, N, train, out, Di + Da, Di)
+        else:
+            zi = self._tower(self.img, ws, st, "pui", x_img, N, train)
+            za = self._tower(self.aud, ws, st, "pua", x_aud, N, train)
+            out = ws.get("p.fused", N * Di)
+            a = 1.0 if self.fusion == "sum" else 0.5      # 0.5 zi + 0.5 za == (zi + za) / 2 exactly
+            out.zero_()
+            ops.axpy(out, zi.view(-1)[:N * Di], a)
+            ops.axpy(out, za.view(-1)[:N * Di], a)
+        if train:
+            st.flush_nbt()
+        return out
 
 
 class LinearProbe:
@@ -95,9 +152,15 @@ class LinearProbe:
     """
 
     def __init__(self, source, kind, D, E=None, lr=1e-4, weight_decay=0.01, act_dtype=F32,
-                 fusion_dropout=0.3, seed=0, classifier_state=None, use_graph=True):
+                 fusion_dropout=0.3, seed=0, classifier_state=None, use_graph=True,
+                 prefix="student", towers=None, fusion="concat"):
+        """prefix: the state-dict prefix of a unimodal ``kind`` ("student" for a DINO model; a
+        SimCLR tower's "image_encoder" / "audio_encoder").  towers: [(kind, prefix) of the image
+        tower, (kind, prefix) of the audio tower] for a late-fusion probe (``fusion``: concat /
+        sum / mean; ``kind`` is then only a label and D the fused width)."""
         dev = source.device
-        self.store = ParamStore(source.spec, dev, has_teacher=source.teacher is not None)
+        self.store = ParamStore(source.spec, dev, has_teacher=source.teacher is not None,
+                                groups=source.groups)
         self.store.student.copy_(source.student)          # copy.deepcopy(model.student)
         self.store.buf_arena.copy_(source.buf_arena)
         source.flush_nbt()
@@ -107,11 +170,14 @@ class LinearProbe:
         self.gm = ops.GEMM_BF16_MFMA if act_dtype == torch.bfloat16 else ops.GEMM_F32_MFMA
         self.act = act_dtype
         self.ws = Workspace(dev)
-        self.multimodal = self.kind in MULTI_ENCODERS
-        if self.multimodal:
+        self.towers = towers is not None
+        self.multimodal = self.towers or self.kind in MULTI_ENCODERS
+        if self.towers:
+            self.enc = _TwoTower(towers, fusion, act_dtype, self.gm)
+        elif self.multimodal:
             self.enc = _MultiEncoder(self.kind, E, D, act_dtype, self.gm, fusion_dropout)
         else:
-            self.enc = _UniEncoder(self.kind, act_dtype, self.gm)
+            self.enc = _UniEncoder(self.kind, act_dtype, self.gm, prefix)
             self.modality = UNI_ENCODERS[self.kind][0]
         self.cls = ParamStore(classifier_sd(D), dev, seed=seed, has_teacher=False)
         if classifier_state is not None:
@@ -134,7 +200,9 @@ class LinearProbe:
             xa = ws.get("p.in.aud", N * 12544, self.act)
             ops.stage_views(images.contiguous(), 1, None, 0, None, N, 784, xi)
             ops.stage_views(audios.contiguous(), 1, None, 0, None, N, 12544, xa)
-            if seed_off is not None:      # device counter: seed + t * StepState.SEED_STRIDE
+            if self.towers:
+                return self.enc(ws, self.store, xi, xa, N, train)
+            if seed_off is not None:     # device counter: seed + t * StepState.SEED_STRIDE
                 return self.enc(ws, self.store, xi, xa, N, train, self.seed * 7919, seed_off)
             return self.enc(ws, self.store, xi, xa, N, train, self.seed * 7919 + self.t)
         src, HW = (images, 784) if self.modality == "image" else (audios, 12544)

@@ -139,7 +139,8 @@ class CSVLogger:
                     if d.startswith("version_") and d.split("_", 1)[1].isdigit()]
             version = max(have) + 1 if have else 0
         self.version = version
-        self.log_dir = os.path.join(root, f"version_{version}")
+        # Lightning: a string version is the directory name itself, a number gives version_{n}
+        self.log_dir = os.path.join(root, version if isinstance(version, str) else f"version_{version}")
         self.metrics_file_path = os.path.join(self.log_dir, "metrics.csv")
         self.metrics, self.metrics_keys = [], []
         self.hparams = {}

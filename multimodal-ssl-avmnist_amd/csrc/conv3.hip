@@ -72,16 +72,28 @@ __device__ __forceinline__ void glds16(const void* g, const bf16* lds_wave) {
 // per-unit base add, every fragment read is an immediate-offset ds_read_b128.
 constexpr int XPAD = 16;
 
-template <int BO, int GPW, int IW8>
+//
+// EV (eval-mode layer, avd_c3_conv_eval): y is never stored.  The epilogue of an item writes its
+// bf16-rounded conv outputs into an LDS tile [pixel][BO + 8] laid over the input / weight buffer
+// the item's last unit has just left, and the block pools that tile: BatchNorm as the fixed
+// affine (scale, shift), ReLU, 2x2 max (floor mode) -> the pooled NHWC map (mode 0) or, for
+// whole maps, its global average (mode 1).  The values and their order are those of
+// conv3p_kernel<EV = false> followed by relu_pool_cl_kernel / relu_pool_gap_cl_kernel
+// (bn_cl.hip), so the result is bit-identical to the two launches.  The unit u+2 DMA that
+// refills that buffer is issued only after the pooling (behind a barrier); the DMA of unit u+1
+// fills the other buffer and was retired by the barrier before the tile is written.
+template <int BO, int GPW, int IW8, bool EV>
 __global__ __launch_bounds__(512, 1) void conv3p_kernel(
     const bf16* __restrict__ x, const bf16* __restrict__ wk, const float* __restrict__ bias,
     bf16* __restrict__ y, float* __restrict__ stats, int N, int H, int W, int C, int O, int TR,
-    int NS, int tilesPS, int xrows, int nitems, int G) {
+    int NS, int tilesPS, int xrows, int nitems, int G, const float* __restrict__ scale,
+    const float* __restrict__ shift, void* __restrict__ pout, int mode) {
   constexpr int NTW = BO / 32;                 // 16-channel tiles per wave
   constexpr int WROWS = 9 * BO;                // weight rows per unit
+  constexpr int TS = BO + 8;                   // EV: tile row stride (elements)
   extern __shared__ __attribute__((aligned(16))) bf16 smem[];
-  float* bs = reinterpret_cast<float*>(smem);  // [O <= 256] bias
-  bf16* buf = smem + 512;                      // 2 x {input [xrows][32], weights [9*BO][32]}
+  float* bs = reinterpret_cast<float*>(smem);  // [O <= 256] bias (EV: + scale, shift)
+  bf16* buf = smem + (EV ? 1536 : 512);        // 2 x {input [xrows][32], weights [9*BO][32]}
   const int bufE = (xrows + WROWS) * CH;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
@@ -95,6 +107,11 @@ __global__ __launch_bounds__(512, 1) void conv3p_kernel(
   const float rW = 1.f / W, rTRW = 1.f / TRW, rIR = 1.f / IR;
 
   for (int i = tid; i < O; i += 512) bs[i] = bias ? bias[i] : 0.f;
+  if constexpr (EV)
+    for (int i = tid; i < O; i += 512) {
+      bs[256 + i] = scale[i];
+      bs[512 + i] = shift[i];
+    }
 
   // lane geometry (the same for every tile): B-read byte offsets for kx = 0..2, and (s, r, xx)
   int xoff[GPW][3], pos[GPW];
@@ -208,7 +225,7 @@ __global__ __launch_bounds__(512, 1) void conv3p_kernel(
       }
     }
     __syncthreads();
-    if (u + 2 < nunits) stage(it0 + (u + 2) / nch, (u + 2) % nch, u & 1);
+    if (!(EV && c == nch - 1) && u + 2 < nunits) stage(it0 + (u + 2) / nch, (u + 2) % nch, u & 1);
     if (c == nch - 1) {
       // ---- epilogue: bias, bf16 rounding, NHWC store, BN sums of the stored values
       const int og = item / tiles, ti = item - og * tiles;
@@ -229,18 +246,22 @@ __global__ __launch_bounds__(512, 1) void conv3p_kernel(
         const int ps = pos[j];
         const int sN = ps >> 16, r = (ps >> 8) & 255, xx = ps & 255;
         if (ps < 0 || y0 + r >= H) continue;
-        bf16* yp = y + ((((size_t)(n0 + sN) * H + y0 + r) * W + xx) * O + cw);
+        // EV: tile row = the pixel's slot (wp + 4j) * 16 + r16 = (sN * TR + r) * W + xx
+        bf16* yp = EV ? buf + (u & 1) * bufE + ((wp + 4 * j) * 16 + r16) * TS + 16 * NTW * wt + 4 * NTW * g
+                      : y + ((((size_t)(n0 + sN) * H + y0 + r) * W + xx) * O + cw);
         uint32_t pk[NTW][2];
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
           const uint32_t lo = pack_bf16x2(acc[j][t][0] + bv[t][0], acc[j][t][1] + bv[t][1]);
           const uint32_t hi = pack_bf16x2(acc[j][t][2] + bv[t][2], acc[j][t][3] + bv[t][3]);
-          const float v[4] = {__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u),
-                              __uint_as_float(hi << 16), __uint_as_float(hi & 0xffff0000u)};
+          if constexpr (!EV) {
+            const float v[4] = {__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u),
+                                __uint_as_float(hi << 16), __uint_as_float(hi & 0xffff0000u)};
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            ss[t][i] += v[i];
-            sq[t][i] = fmaf(v[i], v[i], sq[t][i]);
+            for (int i = 0; i < 4; ++i) {
+              ss[t][i] += v[i];
+              sq[t][i] = fmaf(v[i], v[i], sq[t][i]);
+            }
           }
           pk[t][0] = lo;
           pk[t][1] = hi;
@@ -250,7 +271,69 @@ __global__ __launch_bounds__(512, 1) void conv3p_kernel(
         else
           *reinterpret_cast<uint2*>(yp) = make_uint2(pk[0][0], pk[0][1]);
       }
-      if (stats) {
+      if constexpr (EV) {
+        __syncthreads();                       // the tile is complete
+        const bf16* tile = buf + (u & 1) * bufE;
+        const float* scl = bs + 256 + og * BO;
+        const float* sfl = bs + 512 + og * BO;
+        const int Hp = H / 2, Wp = W / 2, HpT = TR / 2, hp0 = y0 / 2;
+        // relu(bn(.)) of tile pixel p, channel c: load_win's expression (bn_cl.hip)
+        if (mode == 0) {
+          // one thread per (pooled pixel, 8-channel vector): four 16-byte reads, one store
+          constexpr int CV = BO / 8;
+          const int total = NS * HpT * Wp * CV;
+          for (int i = tid; i < total; i += 512) {
+            const int cv = i % CV, pp = i / CV;
+            const int pc = pp % Wp, t2 = pp / Wp;
+            const int pr = t2 % HpT, sN = t2 / HpT;
+            const int n = n0 + sN, hp = hp0 + pr;
+            if (n >= N || hp >= Hp) continue;
+            const int p0 = sN * TRW + 2 * pr * W + 2 * pc;
+            const int poff[4] = {p0, p0 + 1, p0 + W, p0 + W + 1};
+            float mx[8];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const u4 v = *reinterpret_cast<const u4*>(tile + poff[k] * TS + 8 * cv);
+              const unsigned wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+              for (int e = 0; e < 8; ++e) {
+                const float yv = __uint_as_float((e & 1) ? wd[e >> 1] & 0xffff0000u : wd[e >> 1] << 16);
+                const float rv = fmaxf(fmaf(yv, scl[8 * cv + e], sfl[8 * cv + e]), 0.f);
+                if (k == 0 || rv > mx[e]) mx[e] = rv;
+              }
+            }
+            bf16* op = reinterpret_cast<bf16*>(pout) +
+                       ((((size_t)n * Hp + hp) * Wp + pc) * O + og * BO + 8 * cv);
+            *reinterpret_cast<u4*>(op) = u4{pack_bf16x2(mx[0], mx[1]), pack_bf16x2(mx[2], mx[3]),
+                                            pack_bf16x2(mx[4], mx[5]), pack_bf16x2(mx[6], mx[7])};
+          }
+        } else {
+          // whole maps (TR == H): one thread per (sample, channel), the pooled values summed in
+          // relu_pool_gap_cl_kernel's order (hp-major, wp-minor, sequential f32)
+          for (int i = tid; i < NS * BO; i += 512) {
+            const int ch = i % BO, sN = i / BO, n = n0 + sN;
+            if (n >= N) continue;
+            const float sc = scl[ch], sf = sfl[ch];
+            const bf16* tp = tile + sN * TRW * TS + ch;
+            float a = 0.f;
+            for (int hp = 0; hp < Hp; ++hp)
+              for (int wq = 0; wq < Wp; ++wq) {
+                const bf16* q = tp + (2 * hp * W + 2 * wq) * TS;
+                float best = fmaxf(fmaf(bf2f(q[0]), sc, sf), 0.f);
+                const float r1 = fmaxf(fmaf(bf2f(q[TS]), sc, sf), 0.f);
+                const float r2 = fmaxf(fmaf(bf2f(q[W * TS]), sc, sf), 0.f);
+                const float r3 = fmaxf(fmaf(bf2f(q[(W + 1) * TS]), sc, sf), 0.f);
+                if (r1 > best) best = r1;
+                if (r2 > best) best = r2;
+                if (r3 > best) best = r3;
+                a += best;
+              }
+            reinterpret_cast<float*>(pout)[(size_t)n * O + og * BO + ch] = a / (float)(Hp * Wp);
+          }
+        }
+        __syncthreads();                       // every wave has left the tile: refill the buffer
+        if (u + 2 < nunits) stage(it0 + (u + 2) / nch, (u + 2) % nch, u & 1);
+      } else if (stats) {
         // per-block running sums over the tiles of one (og, BatchNorm group): written once per
         // such run (and zeros for the pairs the block never reaches) into row blockIdx*4 + wp
         const int pair = og * G + ti / tilesPG;
@@ -276,7 +359,7 @@ __global__ __launch_bounds__(512, 1) void conv3p_kernel(
         for (int t = 0; t < NTW; ++t) acc[j][t] = f4{0.f, 0.f, 0.f, 0.f};
     }
   }
-  if (stats) {
+  if (!EV && stats) {
     if (cur_pair >= 0) flush(cur_pair);
     // the (og, group) pairs this block never reached: zero rows.  The reached pairs are the
     // contiguous interval [first, last] of the og-major order.
@@ -301,7 +384,9 @@ int iw8_of(int W) { return (W + 2 + XPAD - 1) / XPAD * XPAD; }
 // The tile with the best utilisation of GPW*64 pixel slots (ties: more pixels); whole small
 // maps are packed NS per block with NS | B (a tile never straddles two BatchNorm groups); the
 // two LDS buffers (input rows + a 64-channel weight slice) and the bias fit 160 KB.
-Plan3 plan3(int H, int W, int B) {
+// ev (avd_c3_conv_eval): no BatchNorm groups, so any NS (the kernel guards n < N: ragged batches)
+// and only even TR, so that no 2x2 pooling window straddles two tiles (y0 = tt * TR stays even).
+Plan3 plan3(int H, int W, int B, bool ev = false) {
   Plan3 best{0, 0, 0, 0, 0, 0};
   double bu = -1;
   const int IW8 = iw8_of(W);
@@ -320,8 +405,8 @@ Plan3 plan3(int H, int W, int B) {
     };
     if (H * W <= cap)
       for (int ns = cap / (H * W); ns >= 1; --ns)
-        if (B % ns == 0) consider(H, ns);
-    for (int tr = 1; tr <= H && tr * W <= cap; ++tr) consider(tr, 1);
+        if (ev || B % ns == 0) consider(H, ns);
+    for (int tr = ev ? 2 : 1; tr <= H && tr * W <= cap; tr += ev ? 2 : 1) consider(tr, 1);
   }
   return best;
 }
@@ -345,11 +430,31 @@ int launch3(const Plan3& p, const void* x, const void* wk, const float* bias, vo
   const int nitems = tiles * (O / BO);
   // with statistics every CU's block owns 4 partial rows per group (avd_c3_stat_rows)
   const int grid = stats ? num_cus() : std::min(nitems, num_cus());
-  conv3p_kernel<BO, GPW, IW8><<<grid, 512, lds, st>>>(
+  conv3p_kernel<BO, GPW, IW8, false><<<grid, 512, lds, st>>>(
       (const bf16*)x, (const bf16*)wk, bias, (bf16*)y, stats, N, H, W, C, O, p.TR, p.NS,
-      p.tilesPS, p.xrows, nitems, N / B);
+      p.tilesPS, p.xrows, nitems, N / B, nullptr, nullptr, nullptr, 0);
   AVD_CHECK_LAUNCH();
   return AVD_OK;
+}
+
+// the pooling tile [TP][BO + 8] bf16 lies inside one {input, weights} buffer
+bool tile_fits(const Plan3& p, int W, int BO) {
+  return (size_t)p.NS * p.TR * W * (BO + 8) * 2 <= (size_t)(p.xrows + 9 * BO) * ROWB;
+}
+
+template <int BO, int GPW, int IW8>
+int launch3e(const Plan3& p, const void* x, const void* wk, const float* bias, const float* scale,
+             const float* shift, void* out, int mode, int N, int H, int W, int C, int O,
+             hipStream_t st) {
+  const size_t lds = 3072 + 2 * (size_t)(p.xrows + 9 * BO) * ROWB;
+  const int tiles = avd_cdiv(N, p.NS) * p.tilesPS;       // the last sample group may be ragged
+  const int nitems = tiles * (O / BO);
+  const int grid = std::min(nitems, grid_cap(num_cus()));
+  conv3p_kernel<BO, GPW, IW8, true><<<grid, 512, lds, st>>>(
+      (const bf16*)x, (const bf16*)wk, bias, nullptr, nullptr, N, H, W, C, O, p.TR, p.NS,
+      p.tilesPS, p.xrows, nitems, 1, scale, shift, out, mode);
+  AVD_CHECK_LAUNCH();
+  return 1;
 }
 
 }  // namespace
@@ -380,6 +485,37 @@ int avd_c3_conv(const void* x, const void* wk, const float* bias, void* y, float
   AVD_L(32, 4, 32) AVD_L(32, 4, 16)
 #undef AVD_L
   return AVD_ERR_SHAPE;
+}
+
+// Eval-mode layer in one launch: conv3x3 + BatchNorm from fixed per-channel (scale, shift) +
+// ReLU + 2x2 max-pool (+ global average), bit-identical to avd_cl_conv_fwd (stats = NULL)
+// followed by avd_cl_bn_relu_pool in the same mode, without the conv output in memory.
+extern "C" int avd_c3_eval_serves(int N, int H, int W, int C, int O, int mode) {
+  if (N <= 0 || H < 2 || W < 2 || W > 62 || (mode != 0 && mode != 1)) return 0;
+  if (!avd_c3_serves(AVD_BF16, C, O, 3, 1)) return 0;
+  const Plan3 p = plan3(H, W, N, true);
+  if (!p.NS || !tile_fits(p, W, O % 64 == 0 ? 64 : 32)) return 0;
+  if (3072 + 2 * (size_t)(p.xrows + 9 * 64) * ROWB > 160 * 1024) return 0;
+  if (mode == 1 && p.TR != H) return 0;        // the average needs whole maps in a tile
+  return 1;
+}
+
+// 1 = launched, 0 = not served (the caller keeps the two launches), < 0 = error.
+extern "C" int avd_c3_conv_eval(const void* x, const void* wk, const float* bias,
+                                const float* scale, const float* shift, void* out, int mode,
+                                int N, int H, int W, int C, int O, void* stream) {
+  if (!x || !wk || !scale || !shift || !out) return AVD_ERR_ARG;
+  if (!avd_c3_eval_serves(N, H, W, C, O, mode)) return 0;
+  const Plan3 p = plan3(H, W, N, true);
+  hipStream_t st = avd_stream(stream);
+#define AVD_L(BO_, G, I)                                                                     \
+  if (O % BO_ == 0 && p.GPW == G && p.IW8 == I)                                              \
+    return launch3e<BO_, G, I>(p, x, wk, bias, scale, shift, out, mode, N, H, W, C, O, st);
+  AVD_L(64, 7, 64) AVD_L(64, 7, 32) AVD_L(64, 7, 16) AVD_L(64, 4, 64) AVD_L(64, 4, 32)
+  AVD_L(64, 4, 16) AVD_L(32, 7, 64) AVD_L(32, 7, 32) AVD_L(32, 7, 16) AVD_L(32, 4, 64)
+  AVD_L(32, 4, 32) AVD_L(32, 4, 16)
+#undef AVD_L
+  return 0;
 }
 
 // ============================================================================ weight gradient
