@@ -273,6 +273,55 @@ int avd_xent_fused(const float* q, const float* k, int R, int C, int P, int Bh, 
                    int msk0, int msk1, float inv_t, float gscale, float* loss, float* dq, float* dk,
                    float* ws, long long ws_elems, void* stream);
 
+/* CrossModalAttention.forward (models/dino.py:393-404) for a whole step in one launch (xattn.hip):
+ *   OUT = X + softmax(scale Q K^T) V     per (direction d < dirs, group g < groups),
+ * single-head attention across the B samples of one encoder call (one view; dino.py:678-704 calls
+ * the encoder once per view, CrossAttentionMultiModalEncoder.forward 426-452 runs the two
+ * directions).  Every operand is a strided f32 matrix: group g of direction d is the B rows
+ * starting at  ptr + d * ds + g * B * ld  (ld >= E; ld, ds multiples of 4 floats, ptr 16-byte
+ * aligned, else AVD_ERR_ARG) -- so Q / K / V can be column slices of one projection buffer and
+ * X / OUT the halves of a [rows, 2E] cat (ds = E).  Flash-style on the bf16 MFMA: operands rounded
+ * to bf16, f32 accumulation, online softmax, the scores never stored; keys past B in the last key
+ * tile are excluded from max and sum, query rows past B are not written.  lse (nullable: teacher
+ * and eval passes) [dirs][groups][B] = the row log-sum-exp of scale Q K^T, for avd_xattn_bwd.
+ * E in {32, 64, 128, 256, 512}, B >= 1, groups >= 1, dirs in {1, 2} (else AVD_ERR_SHAPE). */
+int avd_xattn_fwd(const float* q, long long ldq, long long dsq, const float* k, long long ldk,
+                  long long dsk, const float* v, long long ldv, long long dsv, const float* x,
+                  long long ldx, long long dsx, float* out, long long ldo, long long dso, float* lse,
+                  int dirs, int groups, int B, int E, float scale, void* stream);
+/* Backward of the attention term (the residual's dX = dOUT is the caller's): with P recomputed
+ * from lse,  dV = P^T dO,  dP = dO V^T,  dS = P o (dP - rowsum(P o dP)),  dQ = scale dS K,
+ * dK = scale dS^T Q  (rowsum(P o dP) = rowsum(dO o (P V))).  A row pass (delta, dQ) and a column
+ * pass (dK, dV); no B x B array in HBM, no atomics, every sum in a fixed order: two runs are
+ * bit-identical.  ws: avd_xattn_bwd_ws(...) floats (-1: unsupported shape). */
+int avd_xattn_bwd_ws(int dirs, int groups, int B, int E);
+int avd_xattn_bwd(const float* dout, long long lddo, long long dsdo, const float* q, long long ldq,
+                  long long dsq, const float* k, long long ldk, long long dsk, const float* v,
+                  long long ldv, long long dsv, const float* lse, float* dq, long long lddq,
+                  long long dsdq, float* dk, long long lddk, long long dsdk, float* dv,
+                  long long lddv, long long dsdv, float* ws, long long ws_elems, int dirs, int groups,
+                  int B, int E, float scale, void* stream);
+
+/* GatedMultiModalEncoder.forward (models/dino.py:245-259): out[r][c] = sigmoid(gate) cat[r][c]
+ * over the [rows, 2E] cat, gate = *gate_image for c < E and *gate_audio for c >= E, both read
+ * from device memory (no host sync).  Backward: dcat = sigmoid(gate) dout and the two scalar
+ * gradients sigmoid' * sum dout o cat over the half, by a two-stage fixed-order reduction
+ * (ws: avd_gate_bwd_ws floats).  dcat may alias dout (in place). */
+int avd_gate_fwd(const float* cat, long long ldc, const float* gate_image, const float* gate_audio,
+                 float* out, long long ldo, int rows, int E, void* stream);
+int avd_gate_bwd_ws(int rows, int E);
+int avd_gate_bwd(const float* dout, long long ldd, const float* cat, long long ldc,
+                 const float* gate_image, const float* gate_audio, float* dcat, long long lddc,
+                 float* dgate_image, float* dgate_audio, float* ws, long long ws_elems, int rows,
+                 int E, void* stream);
+
+/* Row softmax of the plain attention route (fp32 parity mode: S in HBM between avd_gemm calls;
+ * attn.softmax(dim=-1), dino.py:401), in place: s[r][:C] = softmax(s[r][:C]); and its backward,
+ * in place on dp: dp[r][c] = p[r][c] (dp[r][c] - sum_c' p[r][c'] dp[r][c']). */
+int avd_softmax_rows_fwd(float* s, long long ld, int R, int C, void* stream);
+int avd_softmax_rows_bwd(const float* p, long long ldp, float* dp, long long lddp, int R, int C,
+                         void* stream);
+
 /* Test hook: fill the LDS of every CU with NaN bit patterns (0x7fc07fc0), so a kernel that reads
  * LDS it never wrote sees NaN instead of a benign leftover (tools/lds_poison.py). */
 int avd_lds_poison(void* stream);

@@ -73,6 +73,15 @@ PROTOS = {
     "avd_lds_poison": [P],
     "avd_xent_fused_ws": [I, I, I],
     "avd_xent_fused": [P, P, I, I, I, I, I, I, I, I, F, F, P, P, P, P, L, P],
+    "avd_xattn_fwd": [P, L, L, P, L, L, P, L, L, P, L, L, P, L, L, P, I, I, I, I, F, P],
+    "avd_xattn_bwd_ws": [I, I, I, I],
+    "avd_xattn_bwd": [P, L, L, P, L, L, P, L, L, P, L, L, P, P, L, L, P, L, L, P, L, L, P, L,
+                      I, I, I, I, F, P],
+    "avd_gate_fwd": [P, L, P, P, P, L, I, I, P],
+    "avd_gate_bwd_ws": [I, I],
+    "avd_gate_bwd": [P, L, P, L, P, P, P, L, P, P, P, L, I, I, P],
+    "avd_softmax_rows_fwd": [P, L, I, I, P],
+    "avd_softmax_rows_bwd": [P, L, P, L, I, I, P],
     "avd_cl_layer_bwd_slabs": [I, I, I, I, I, I, I, I],
     "avd_cl_layer_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     "avd_cl_layer_bwd_codes": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],

@@ -13,6 +13,7 @@ before a host point (a segment, like any captured graph, ends with every forked 
 rejoined); callers join exactly there and nowhere else.
 """
 import collections
+import gc
 
 import torch
 
@@ -146,6 +147,23 @@ class GraphedStep:
             return
         if _ACTIVE is not None:
             raise RuntimeError("nested step capture")
+        # No finaliser of a GPU object may run inside the capture.  Engines and probes are
+        # cyclic garbage (engine <-> its GraphedStep), so their captured graphs die whenever the
+        # cycle collector next runs -- and on ROCm >= 6.2 torch's ~CUDAGraph synchronises the
+        # device, which is an error while a stream captures, raised inside a destructor: the
+        # process aborts.  So collect what is dead now, at a point where the device may be
+        # synchronised, and keep the collector off until the capture has ended.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            self._capture(key, body)
+        finally:
+            if gc_was_on:
+                gc.enable()
+
+    def _capture(self, key, body):
+        global _ACTIVE
         torch.cuda.synchronize()
         if self.pool is None:
             self.pool = torch.cuda.graph_pool_handle()

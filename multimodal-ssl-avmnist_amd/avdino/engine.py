@@ -24,7 +24,8 @@ import torch
 
 from . import contrastive, ops
 from .capture import GraphedStep, host_point, new_event  # noqa: F401  (GraphedStep re-exported)
-from .spec import HEAD_NAMES, MULTI_ENCODERS, PROJ_HIDDEN, UNI_ALIASES, UNI_ENCODERS
+from .spec import (HEAD_NAMES, MIX_KIND, MULTI_ENCODERS, PROJ_HIDDEN, UNI_ALIASES, UNI_ENCODERS,
+                   XATTN_NAMES)
 
 F32 = torch.float32
 # early gradient buckets at a host point inside the step (False: one all-reduce after the step)
@@ -816,13 +817,74 @@ def _exchange_finish(hook, grad, ranges=None):
 
 
 # ============================================================================ multimodal DINO
+def _xattn_mats(t, rows, E):
+    """Q, K, V operands of both directions in a [2][rows][3E] projection buffer."""
+    return [(t, c * E, 3 * E, rows * 3 * E) for c in range(3)]
+
+
+def mix_forward(kind, ws, st, prefix, cat, V, B, E, gm, fused, tag, train=False):
+    """The stage between the cat [N, 2E] of the two towers' features and fusion, over rows
+    [0, V*B) in V groups of B (one group per encoder call of the reference): -> (fusion's input
+    [V*B, 2E], context for the backward).  kind (spec.MIX_KIND):
+    None: the cat itself (SimpleMultiModalEncoder / CentralMultiModalEncoder).
+    gated: sigmoid(gate_image / gate_audio) * the two halves (dino.py:245-259).
+    xattn: CrossModalAttention both ways (dino.py:393-404, 426-452) -- q_proj / kv_proj of each
+    direction over all groups at once into one [2][V*B][3E] buffer (Q | K | V columns), then one
+    avd_xattn_fwd launch for all groups and both directions (fused), or avd_gemm + a row softmax
+    per group with P [2][V][B][B] in HBM (plain; P kept for the backward)."""
+    if kind is None:
+        return cat, None
+    rows = V * B
+    mix = ws.get(tag + ".mix", rows * 2 * E)
+    if kind == "gated":
+        ops.gate_fwd(cat, st[prefix + ".gate_image"], st[prefix + ".gate_audio"], mix, rows, E)
+        return mix, None
+    qkv = ws.get(tag + ".qkv", 2 * rows * 3 * E)
+    for d, att in enumerate(XATTN_NAMES):
+        # direction d: queries from half d of the cat, keys / values from the other half
+        key, base = f"{prefix}.{att}", d * rows * 3 * E
+        ops.linear_fwd(cat, st[key + ".q_proj.weight"], st[key + ".q_proj.bias"], qkv, rows,
+                       x_ld=2 * E, x_off=d * E, out_ld=3 * E, out_off=base, mode=gm)
+        ops.linear_fwd(cat, st[key + ".kv_proj.weight"], st[key + ".kv_proj.bias"], qkv, rows,
+                       x_ld=2 * E, x_off=(1 - d) * E, out_ld=3 * E, out_off=base + E, mode=gm)
+    scale = E ** -0.5
+    q, k, v = _xattn_mats(qkv, rows, E)
+    if fused:
+        lse = ws.get(tag + ".lse", 2 * rows) if train else None
+        ops.xattn_fwd(q, k, v, (cat, 0, 2 * E, E), (mix, 0, 2 * E, E), lse, 2, V, B, E, scale)
+        return mix, (qkv, lse)
+    pm = ws.get(tag + ".attn_p", 2 * rows * B)
+    for d in range(2):
+        for g in range(V):
+            r0 = d * rows + g * B
+            ops.gemm(B, B, E, qkv, 3 * E, 1, qkv, 1, 3 * E, pm, B, alpha=scale, a_off=r0 * 3 * E,
+                     b_off=r0 * 3 * E + E, c_off=r0 * B, mode=gm)
+    ops.softmax_rows_fwd(pm, 2 * rows, B)
+    mix.view(rows, 2 * E).copy_(cat[:rows * 2 * E].view(rows, 2 * E))     # the residual
+    for d in range(2):
+        for g in range(V):
+            r0 = d * rows + g * B
+            ops.gemm(B, E, B, pm, B, 1, qkv, 3 * E, 1, mix, 2 * E, beta=1.0, a_off=r0 * B,
+                     b_off=r0 * 3 * E + 2 * E, c_off=g * B * 2 * E + d * E, mode=gm)
+    return mix, (qkv, pm)
+
+
 class MultiCentralEngine:
     """Training step of MultiModalDINO{,WithMSE,WithINFONCE,SemiSupervised} over
     CentralMultiModalEncoder (``--model multi_central``, dino.py:454-468) or
     SimpleMultiModalEncoder (``--model multi_simple``, dino.py:214-234: the 3x3 image_encoder /
     audio_encoder with global average pooling), ``--training_mode {default,mse,infonce,
     semi_supervised}``.  Both encoders are the same dataflow -- two conv branches, each a
-    Linear to E, cat, fusion -- so only the stacks and the Linear keys differ."""
+    Linear to E, cat, fusion -- so only the stacks and the Linear keys differ.
+    GatedMultiModalEncoder (``multi_simple_gated``, dino.py:237-259) and
+    CrossAttentionMultiModalEncoder (``multi_cross_attention``, dino.py:385-452) run multi_simple's
+    towers with a "mix" stage between the cat and fusion (``_mix_fwd`` / ``_mix_bwd``): it acts on
+    the views' rows [0, V*B) in groups of B (the reference calls the encoder once per view); the
+    originals' rows feed the mse / infonce / semi heads unmixed (dino.py:1168-1169)."""
+
+    # cross-attention route: the fused flash-style kernel (avd_xattn_fwd / _bwd) in the bf16 step;
+    # False (and always in the fp32 parity mode): avd_gemm + row softmax per group, S in HBM
+    XATTN_FUSED = True
 
     def __init__(self, store, mode, E, D, P, hp, act_dtype=F32, grad_hook=None, seed=0,
                  buffer_hook=None, negatives="global", group=None, concurrent=True, conv_fp8=False,
@@ -838,6 +900,9 @@ class MultiCentralEngine:
         self.conv_fp8 = bool(conv_fp8) and act_dtype == torch.bfloat16
         self.encoder = encoder
         istack, self.img_lin, astack, self.aud_lin, _sd = MULTI_ENCODERS[encoder]
+        self.mix = MIX_KIND.get(encoder)          # None (plain cat) | "gated" | "xattn"
+        if self.mix == "xattn" and E not in ops.XATTN_DIMS:
+            raise ValueError(f"{encoder}: encoder_output_dim must be one of {ops.XATTN_DIMS} (got {E})")
         # bf16: the flatten tails stay NHWC bf16 and the encoder Linears run on the (h, w, c)
         # ordered kernels (avd_linear_*_hwc) with a per-step bf16 copy of their weights
         hwc = self.HWC and act_dtype == torch.bfloat16
@@ -989,6 +1054,64 @@ class MultiCentralEngine:
         self._linear_fwd(prefix, "aud", ab, fa, cat, N, E)
         return cat, (fi, ci, fa, ca)
 
+    def _xattn_fused(self):
+        return self.XATTN_FUSED and self.act == torch.bfloat16
+
+    def _mix_fwd(self, prefix, cat, V, B, tag, ws=None, train=False):
+        return mix_forward(self.mix, ws or self.ws, self.store, prefix, cat, V, B, self.E, self.gm,
+                           self._xattn_fused(), tag, train)
+
+    def _mix_bwd(self, mctx, cat, dcat, V, B):
+        """Backward of ``_mix_fwd`` in place on dcat rows [0, V*B): in, the gradient of fusion's
+        input; out, the gradient of the cat.  Writes the gate / attention parameter gradients.
+        xattn: dcat keeps the residual term and collects the q-projection backward of each half's
+        own direction and the kv-projection backward of the other direction."""
+        ws, st, E = self.ws, self.store, self.E
+        rows = V * B
+        if self.mix == "gated":
+            gi, ga = "student.gate_image", "student.gate_audio"
+            gws = ws.get("gate_ws", ops.gate_bwd_ws(rows, E))
+            ops.gate_bwd(dcat, cat, st[gi], st[ga], dcat, st.grad_of(gi), st.grad_of(ga), gws, rows, E)
+            return
+        qkv, saved = mctx
+        dqkv = ws.get("s.dqkv", 2 * rows * 3 * E)
+        scale = E ** -0.5
+        q, k, v = _xattn_mats(qkv, rows, E)
+        dq, dk, dv = _xattn_mats(dqkv, rows, E)
+        if self._xattn_fused():
+            xws = ws.get("xattn_ws", ops.xattn_bwd_ws(2, V, B, E))
+            ops.xattn_bwd((dcat, 0, 2 * E, E), q, k, v, saved, dq, dk, dv, xws, 2, V, B, E, scale)
+        else:
+            pm = saved
+            dsm = ws.get("s.attn_ds", 2 * rows * B)
+            for d in range(2):
+                for g in range(V):
+                    r0, o0 = d * rows + g * B, g * B * 2 * E + d * E
+                    # dP = dO V^T ; dV = P^T dO
+                    ops.gemm(B, B, E, dcat, 2 * E, 1, qkv, 1, 3 * E, dsm, B, a_off=o0,
+                             b_off=r0 * 3 * E + 2 * E, c_off=r0 * B, mode=self.gm)
+                    ops.gemm(B, E, B, pm, 1, B, dcat, 2 * E, 1, dqkv, 3 * E, a_off=r0 * B, b_off=o0,
+                             c_off=r0 * 3 * E + 2 * E, mode=self.gm)
+            ops.softmax_rows_bwd(pm, dsm, 2 * rows, B)
+            for d in range(2):
+                for g in range(V):
+                    r0 = d * rows + g * B
+                    # dQ = scale dS K ; dK = scale dS^T Q
+                    ops.gemm(B, E, B, dsm, B, 1, qkv, 3 * E, 1, dqkv, 3 * E, alpha=scale, a_off=r0 * B,
+                             b_off=r0 * 3 * E + E, c_off=r0 * 3 * E, mode=self.gm)
+                    ops.gemm(B, E, B, dsm, 1, B, qkv, 3 * E, 1, dqkv, 3 * E, alpha=scale, a_off=r0 * B,
+                             b_off=r0 * 3 * E, c_off=r0 * 3 * E + E, mode=self.gm)
+        for d, att in enumerate(XATTN_NAMES):
+            key, base = f"student.{att}", d * rows * 3 * E
+            for proj, O, col, half in ((".q_proj", E, 0, d), (".kv_proj", 2 * E, E, 1 - d)):
+                w = st[key + proj + ".weight"]
+                ops.linear_bwd(dqkv, cat, w, st.grad_of(key + proj + ".weight"),
+                               st.grad_of(key + proj + ".bias"), None, rows, dout_ld=3 * E,
+                               dout_off=base + col, x_ld=2 * E, x_off=half * E, mode=self.gm)
+                # dcat[:, half] += d(proj out) W
+                ops.gemm(rows, E, O, dqkv, 3 * E, 1, w, E, 1, dcat, 2 * E, beta=1.0, a_off=base + col,
+                         c_off=half * E, mode=self.gm)
+
     def _fusion_fwd(self, prefix, cat, rows, tag, seed, ws=None, seed_off=None):
         """fusion: Linear(2E,E) -> ReLU -> Dropout(0.3, hard-coded dino.py:204/215) -> Linear(E,D)."""
         ws, st, E, D = ws or self.ws, self.store, self.E, self.D
@@ -1132,7 +1255,8 @@ class MultiCentralEngine:
         tcat, _ = self._encoder_fwd("teacher", self.t_img, self.t_aud, x_img[:G * B * 784],
                                     x_aud[:G * B * 12544], G * B, G, "t", need_dgrad=False, ws=tws,
                                     wts=wts)
-        tout, _ = self._fusion_fwd("teacher", tcat, G * B, "t", base + 2, ws=tws, seed_off=seed_off)
+        tmix, _ = self._mix_fwd("teacher", tcat, G, B, "t", ws=tws)
+        tout, _ = self._fusion_fwd("teacher", tmix, G * B, "t", base + 2, ws=tws, seed_off=seed_off)
         t_proj = tws.get("t_proj", G * B * self.P)
         self.tproj.forward(tws, st, "tp", tout, G * B, t_proj, 0.0, 0)
         ops.mark("t.end")
@@ -1247,7 +1371,8 @@ class MultiCentralEngine:
                 (head_out, hctx), h_done = self._on_side(heads)
             n_parts = V * B + B
         ops.mark("s.enc")
-        fout, sfus = self._fusion_fwd("student", cat, V * B, "s", base + 1)
+        mix, mctx = self._mix_fwd("student", cat, V, B, "s", train=training)
+        fout, sfus = self._fusion_fwd("student", mix, V * B, "s", base + 1)
         s_proj = ws.get("s_proj", V * B * P)
         spc = self.sproj.forward(ws, st, "sp", fout, V * B, s_proj, hp.dropout, base + 3,
                                  seed_off=self.sstate.seed_off)
@@ -1270,8 +1395,8 @@ class MultiCentralEngine:
         ops.sum_to(loss_parts, n_parts, 1.0, loss)
         ops.mark("loss")
         self.fwd_count += 1
-        self.last = dict(B=B, G=G, L=L, V=V, NG=NG, N=N, cat=cat, senc=senc, sfus=sfus, spc=spc,
-                         ds=ds, hctx=hctx, center_new=center_new, loss=loss, s_proj=s_proj,
+        self.last = dict(B=B, G=G, L=L, V=V, NG=NG, N=N, cat=cat, mix=mix, mctx=mctx, senc=senc,
+                         sfus=sfus, spc=spc, ds=ds, hctx=hctx, center_new=center_new, loss=loss, s_proj=s_proj,
                          t_proj=t_proj, training=training, head_out=head_out)
         st.flush_nbt()
         return loss
@@ -1340,9 +1465,12 @@ class MultiCentralEngine:
             ops.act_bwd(h, dr, dh, 0, None, None, V * B, 1, E, self.hp.fusion_dropout,
                         ((self.seed * 1000003) & SEED_MASK) + 1, self.sstate.seed_off)
             yield
-            ops.linear_bwd(dh, c["cat"], st["student.fusion.0.weight"], st.grad_of("student.fusion.0.weight"),
+            ops.linear_bwd(dh, c["mix"], st["student.fusion.0.weight"], st.grad_of("student.fusion.0.weight"),
                            st.grad_of("student.fusion.0.bias"), dcat, V * B, x_ld=2 * E, dx_ld=2 * E,
                            mode=self.gm)
+            if self.mix is not None:
+                yield
+                self._mix_bwd(c["mctx"], c["cat"], dcat, V, B)
 
         def drain(gen):
             for _ in gen:

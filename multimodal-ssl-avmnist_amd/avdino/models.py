@@ -5,6 +5,9 @@ the reference (paths relative to its AVMNIST_Experiments/):
 
   CentralMultiModalEncoder          models/dino.py:454-468   (``--model multi_central``)
   SimpleMultiModalEncoder           models/dino.py:214-234   (``--model multi_simple``)
+  GatedMultiModalEncoder            models/dino.py:237-259   (``--model multi_simple_gated``)
+  CrossAttentionMultiModalEncoder   models/dino.py:407-452   (``--model multi_cross_attention``)
+  CrossModalAttention               models/dino.py:385-404
   ProjectionHead                    models/dino.py:1240-1254
   MultiModalDINO                    models/dino.py:588-727
   MultiModalDINOWithMSE             models/dino.py:1156-1171
@@ -83,6 +86,47 @@ class CentralMultiModalEncoder(BaseMultiModalEncoder):
         super().__init__(output_dim, encoder_output_dim, fusion_dropout=0.3)
 
 
+class GatedMultiModalEncoder(SimpleMultiModalEncoder):
+    """SimpleMultiModalEncoder with two learnable scalar gates (initial value 0.5):
+    cat([sigmoid(gate_image) * image_features, sigmoid(gate_audio) * audio_features]) feeds
+    fusion (models/dino.py:237-259).  Like the reference's, the constructor takes no
+    fusion_dropout: the base default 0.3 holds."""
+
+    arch = "multi_simple_gated"
+
+    def __init__(self, output_dim=256, encoder_output_dim=512):
+        super().__init__(output_dim, encoder_output_dim)
+
+
+class CrossModalAttention:
+    """q_proj Linear(dim, dim), kv_proj Linear(dim, 2 dim), scale dim^-0.5; forward(x1, x2) =
+    x1 + softmax(q_proj(x1) k^T scale) v with k, v = kv_proj(x2).chunk(2) -- attention across
+    the samples of the call (models/dino.py:385-404).  Descriptor: the compute is
+    avd_xattn_fwd / avd_xattn_bwd (csrc/xattn.hip)."""
+
+    SUPPORTED_DIMS = ops.XATTN_DIMS
+
+    def __init__(self, dim):
+        if dim not in self.SUPPORTED_DIMS:
+            raise ValueError(f"CrossModalAttention: dim must be one of {self.SUPPORTED_DIMS} "
+                             f"(the fused attention kernel's head sizes), got {dim}")
+        self.dim = dim
+        self.scale = dim ** -0.5
+
+
+class CrossAttentionMultiModalEncoder(SimpleMultiModalEncoder):
+    """SimpleMultiModalEncoder whose features attend to the other modality both ways before
+    fusion: cat([image_to_audio_attention(image, audio), audio_to_image_attention(audio,
+    image)]) (models/dino.py:407-452)."""
+
+    arch = "multi_cross_attention"
+
+    def __init__(self, output_dim=256, encoder_output_dim=512, fusion_dropout=0.3):
+        super().__init__(output_dim, encoder_output_dim, fusion_dropout)
+        self.image_to_audio_attention = CrossModalAttention(dim=encoder_output_dim)
+        self.audio_to_image_attention = CrossModalAttention(dim=encoder_output_dim)
+
+
 class ProjectionHead:
     """Linear(in, 512) -> BatchNorm1d -> GELU -> Dropout -> Linear(512, out) (dino.py:1240-1254)."""
 
@@ -118,7 +162,9 @@ class SpectrogramEncoderCentral(SpectrogramEncoder):
     kind = "spectrogram_central"
 
 
-MODEL_MAP = {"multi_simple": SimpleMultiModalEncoder, "multi_central": CentralMultiModalEncoder}
+MODEL_MAP = {"multi_simple": SimpleMultiModalEncoder, "multi_simple_gated": GatedMultiModalEncoder,
+             "multi_cross_attention": CrossAttentionMultiModalEncoder,
+             "multi_central": CentralMultiModalEncoder}
 UNIMODAL_MODEL_MAP = {"image_simple": ImageEncoder, "spectrogram_simple": SpectrogramEncoder,
                       "spectrogram_central": SpectrogramEncoderCentral}
 
@@ -359,7 +405,7 @@ class MultiModalDINO(_ArenaModule):
         if getattr(enc, "arch", None) not in MULTI_ENCODERS:
             raise NotImplementedError(
                 f"{encoder_class.__name__}: the MI355X engine runs {sorted(MULTI_ENCODERS)} "
-                f"(SimpleMultiModalEncoder / CentralMultiModalEncoder)")
+                f"(Simple / Gated / CrossAttention / Central MultiModalEncoder)")
         self.student_spec = enc
         self.projection_dim, self.output_dim = projection_dim, output_dim
         self.encoder_output_dim = encoder_output_dim

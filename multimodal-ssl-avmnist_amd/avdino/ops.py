@@ -1055,6 +1055,113 @@ def xent_fused(q, k, R, C, P, Bh, tgt, msk, inv_t, gscale, loss, dq, dk, ws):
                         int(msk[1]), inv_t, gscale, p(loss), p(dq), p(dk), p(ws), ws.numel(), stream()))
 
 
+# ---------------------------------------------------------------- fusion-encoder mix stage
+XATTN_DIMS = (32, 64, 128, 256, 512)     # encoder_output_dim the fused attention serves
+
+
+def _xmat(m, dirs, groups, B, E, what):
+    """A strided attention operand (tensor, element offset, ld, direction stride): group g of
+    direction d = rows at off + d ds + g B ld.  Checks that everything the kernel may touch
+    lies inside the tensor; returns (address, ld, ds)."""
+    t, off, ld, ds = m
+    _need(t.dtype == torch.float32 and t.is_contiguous(), f"xattn {what}: contiguous f32")
+    _need(ld >= E and ld % 4 == 0 and ds % 4 == 0 and off % 4 == 0 and ds >= 0 and off >= 0,
+          f"xattn {what}: ld >= E, ld / offset / direction stride multiples of 4")
+    _need(off + (dirs - 1) * ds + (groups * B - 1) * ld + E <= t.numel(), f"xattn {what} bounds")
+    return t.data_ptr() + 4 * off, ld, ds
+
+
+def _xdims(dirs, groups, B, E):
+    _need(E in XATTN_DIMS, f"fused cross-attention: E must be one of {XATTN_DIMS} (got {E})")
+    _need(B >= 1 and groups >= 1 and dirs in (1, 2), "xattn: B, groups >= 1, dirs in (1, 2)")
+
+
+def xattn_fwd(q, k, v, x, out, lse, dirs, groups, B, E, scale):
+    """OUT = X + softmax(scale Q K^T) V per (direction, group) in one launch (avd_xattn_fwd);
+    operands are (tensor, offset, ld, direction stride); lse [dirs*groups*B] or None."""
+    _xdims(dirs, groups, B, E)
+    a = [_xmat(m, dirs, groups, B, E, n) for m, n in ((q, "q"), (k, "k"), (v, "v"), (x, "x"), (out, "out"))]
+    _need(lse is None or (lse.dtype == torch.float32 and lse.is_contiguous()
+                          and lse.numel() >= dirs * groups * B), "xattn lse size")
+    flat = [y for m in a for y in m]
+    n = dirs * groups * B
+    _timed(f"xattn_fwd[{dirs}x{groups}x{B}x{E}]", 4 * 5 * n * E, 4 * n * B * E,
+           lambda: call("avd_xattn_fwd", *flat, p(lse), dirs, groups, B, E, scale, stream()))
+
+
+def xattn_bwd_ws(dirs, groups, B, E):
+    _xdims(dirs, groups, B, E)
+    return lib.avd_xattn_bwd_ws(dirs, groups, B, E)
+
+
+def xattn_bwd(dout, q, k, v, lse, dq, dk, dv, ws, dirs, groups, B, E, scale):
+    """dQ, dK, dV of the attention term from dOUT, Q, K, V and the forward's lse (avd_xattn_bwd)."""
+    _xdims(dirs, groups, B, E)
+    a = [_xmat(m, dirs, groups, B, E, n) for m, n in ((dout, "dout"), (q, "q"), (k, "k"), (v, "v"))]
+    g = [_xmat(m, dirs, groups, B, E, n) for m, n in ((dq, "dq"), (dk, "dk"), (dv, "dv"))]
+    n = dirs * groups * B
+    _need(lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= n, "xattn lse size")
+    _need(ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= xattn_bwd_ws(dirs, groups, B, E),
+          "xattn workspace")
+    _timed(f"xattn_bwd[{dirs}x{groups}x{B}x{E}]", 4 * 7 * n * E, 14 * n * B * E,
+           lambda: call("avd_xattn_bwd", *[y for m in a for y in m], p(lse), *[y for m in g for y in m],
+                        p(ws), ws.numel(), dirs, groups, B, E, scale, stream()))
+
+
+def _rows2e(t, off, ld, rows, E, what):
+    _need(t.dtype == torch.float32 and t.is_contiguous() and ld >= 2 * E and off >= 0
+          and off + (rows - 1) * ld + 2 * E <= t.numel(), f"gate {what} bounds")
+    return t.data_ptr() + 4 * off
+
+
+def gate_fwd(cat, gate_image, gate_audio, out, rows, E, cat_ld=None, cat_off=0, out_ld=None, out_off=0):
+    """out = [sigmoid(gate_image) cat[:, :E], sigmoid(gate_audio) cat[:, E:]] (avd_gate_fwd)."""
+    cat_ld = 2 * E if cat_ld is None else cat_ld
+    out_ld = 2 * E if out_ld is None else out_ld
+    _need(rows >= 1 and E >= 1, "gate shapes")
+    _need(gate_image.numel() == 1 and gate_audio.numel() == 1, "gates are scalars")
+    call("avd_gate_fwd", _rows2e(cat, cat_off, cat_ld, rows, E, "cat"), cat_ld, p(gate_image), p(gate_audio),
+         _rows2e(out, out_off, out_ld, rows, E, "out"), out_ld, rows, E, stream())
+
+
+def gate_bwd_ws(rows, E):
+    n = lib.avd_gate_bwd_ws(rows, E)
+    _need(n > 0, "gate shapes")
+    return n
+
+
+def gate_bwd(dout, cat, gate_image, gate_audio, dcat, dgate_image, dgate_audio, ws, rows, E,
+             dout_ld=None, cat_ld=None, dcat_ld=None):
+    """dcat = sigmoid(gate) dout; dgate = sigmoid'(gate) sum(dout o cat) per half (avd_gate_bwd)."""
+    dout_ld = 2 * E if dout_ld is None else dout_ld
+    cat_ld = 2 * E if cat_ld is None else cat_ld
+    dcat_ld = 2 * E if dcat_ld is None else dcat_ld
+    _need(rows >= 1 and E >= 1, "gate shapes")
+    for g in (gate_image, gate_audio, dgate_image, dgate_audio):
+        _need(g.numel() == 1 and g.dtype == torch.float32, "gates are f32 scalars")
+    _need(ws.dtype == torch.float32 and ws.numel() >= gate_bwd_ws(rows, E), "gate workspace")
+    call("avd_gate_bwd", _rows2e(dout, 0, dout_ld, rows, E, "dout"), dout_ld,
+         _rows2e(cat, 0, cat_ld, rows, E, "cat"), cat_ld, p(gate_image), p(gate_audio),
+         _rows2e(dcat, 0, dcat_ld, rows, E, "dcat"), dcat_ld, p(dgate_image), p(dgate_audio), p(ws),
+         ws.numel(), rows, E, stream())
+
+
+def softmax_rows_fwd(s, R, C, ld=None):
+    ld = C if ld is None else ld
+    _need(s.dtype == torch.float32 and s.is_contiguous() and R >= 1 and C >= 1 and ld >= C
+          and (R - 1) * ld + C <= s.numel(), "softmax rows bounds")
+    call("avd_softmax_rows_fwd", p(s), ld, R, C, stream())
+
+
+def softmax_rows_bwd(pr, dp, R, C, ldp=None, lddp=None):
+    ldp = C if ldp is None else ldp
+    lddp = C if lddp is None else lddp
+    for t, ld in ((pr, ldp), (dp, lddp)):
+        _need(t.dtype == torch.float32 and t.is_contiguous() and R >= 1 and C >= 1 and ld >= C
+              and (R - 1) * ld + C <= t.numel(), "softmax rows bounds")
+    call("avd_softmax_rows_bwd", p(pr), ldp, p(dp), lddp, R, C, stream())
+
+
 def cosine_consistency(emb, V, B, D, alpha, loss_parts, demb):
     _need(emb.numel() >= V * B * D and (demb is None or demb.numel() >= V * B * D)
           and (loss_parts is None or loss_parts.numel() >= B), "cosine consistency shapes")

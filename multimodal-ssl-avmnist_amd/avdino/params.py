@@ -25,11 +25,13 @@ from collections import OrderedDict
 
 import torch
 
+from .spec import GATE_INIT
+
 ALIGN = 16  # floats (64 B) per parameter slot
 
 
 def _is_param(kind):
-    return kind in ("w", "b", "bn_w", "bn_b")
+    return kind in ("w", "b", "bn_w", "bn_b", "gate")
 
 
 def _dead(key):
@@ -162,8 +164,8 @@ class ParamStore:
     # ------------------------------------------------------------------ init / io
     def reset_parameters(self, seed=0):
         """PyTorch's default init for the reference layers (Conv2d/Linear kaiming-uniform(a=sqrt 5)
-        => U(+-1/sqrt(fan_in)) for weight and bias; BN weight 1, bias 0); the teacher starts as an
-        exact copy of the student (dino.py:615-629)."""
+        => U(+-1/sqrt(fan_in)) for weight and bias; BN weight 1, bias 0; the fusion
+        gates 0.5); the teacher starts as an exact copy of the student (dino.py:615-629)."""
         g = torch.Generator().manual_seed(seed)
         fan = {}
         for k, (shape, kind) in self.spec.items():
@@ -176,6 +178,8 @@ class ParamStore:
                 v = (torch.rand(shape, generator=g, dtype=torch.float64) * 2 - 1) * b
             elif kind == "bn_w":
                 v = torch.ones(shape, dtype=torch.float64)
+            elif kind == "gate":
+                v = torch.full(shape, GATE_INIT, dtype=torch.float64)
             else:
                 v = torch.zeros(shape, dtype=torch.float64)
             self[k].copy_(v.to(torch.float32))

@@ -21,9 +21,9 @@ import torch
 
 from . import ops
 from .capture import GraphedStep
-from .engine import F32, ConvBranch, StepState, UniEncoder, Workspace
+from .engine import F32, ConvBranch, MultiCentralEngine, StepState, UniEncoder, Workspace, mix_forward
 from .params import ParamStore
-from .spec import MULTI_ENCODERS, UNI_ALIASES, UNI_ENCODERS
+from .spec import MIX_KIND, MULTI_ENCODERS, UNI_ALIASES, UNI_ENCODERS
 
 from collections import OrderedDict
 
@@ -40,7 +40,9 @@ def classifier_sd(D, hidden=128, num_classes=10):
 class _MultiEncoder:
     """The multimodal student (SimpleMultiModalEncoder.forward, dino.py:229-234; the
     CentralMultiModalEncoder of 454-468 or the 3x3 encoders of 214-227) without gradients:
-    both conv branches, their Linears into the cat buffer, fusion."""
+    both conv branches, their Linears into the cat buffer, the gated / cross-attention encoders'
+    mix stage (engine.mix_forward; one group = the whole batch of the call, as the reference's
+    single encoder call), fusion."""
 
     def __init__(self, arch, E, D, act, gm, fusion_dropout):
         self.E, self.D, self.gm, self.p = E, D, gm, fusion_dropout
@@ -48,6 +50,10 @@ class _MultiEncoder:
         self.img = ConvBranch(istack("student"), act)
         self.aud = ConvBranch(astack("student"), act)
         self.ilin, self.alin = "student." + ilin, "student." + alin
+        self.mix = MIX_KIND.get(arch)
+        self.fused = MultiCentralEngine.XATTN_FUSED and act == torch.bfloat16
+        if self.mix == "xattn" and E not in ops.XATTN_DIMS:
+            raise ValueError(f"{arch}: encoder_output_dim must be one of {ops.XATTN_DIMS} (got {E})")
 
     def __call__(self, ws, st, x_img, x_aud, N, train, seed, seed_off=None):
         E = self.E
@@ -63,6 +69,7 @@ class _MultiEncoder:
                        cat, N, out_ld=2 * E, out_off=0, mode=self.gm)
         ops.linear_fwd(fa, st[self.alin + ".weight"], st[self.alin + ".bias"],
                        cat, N, out_ld=2 * E, out_off=E, mode=self.gm)
+        cat, _ = mix_forward(self.mix, ws, st, "student", cat, 1, N, E, self.gm, self.fused, "p")
         h = ws.get("p.fh", N * E)
         ops.linear_fwd(cat, st["student.fusion.0.weight"], st["student.fusion.0.bias"], h, N,
                        x_ld=2 * E, mode=self.gm)

@@ -182,19 +182,20 @@ def _stack_macs(stack):
     return macs
 
 
-def model_stats(model, G, L):
+def model_stats(model, G, L, B=1):
     """(GFLOPs per sample, parameter count) for run_dino's performance summary
     (calculate_gflops, run_dino.py:243-283: torchinfo's total_mult_adds of the eval-mode forward
     over one batch / batch size, and total_params).  Analytic here (no torchinfo): Conv2d and
     Linear multiply-adds of the student over the G+L views, the teacher over the G global views,
     their projection heads and, for the modes with heads, the originals through the student
-    branches and both heads; parameters = every parameter tensor of the state dict (student,
+    branches and both heads; the cross-attention encoder's attention products grow with the batch
+    size B of a call; parameters = every parameter tensor of the state dict (student,
     teacher, heads, incl. the CentralNet fc1/fc2 the reference builds but never runs)."""
-    from .spec import MULTI_ENCODERS, UNI_ENCODERS
+    from .spec import MIX_KIND, MULTI_ENCODERS, UNI_ENCODERS, XATTN_NAMES
     m = model.model
     spec = m.store.spec
     params = sum(int(math.prod(shp)) for k, (shp, kind) in spec.items()
-                 if kind in ("w", "b", "bn_w", "bn_b"))
+                 if kind in ("w", "b", "bn_w", "bn_b", "gate"))
 
     def lin(key):
         shp = spec[key + ".weight"][0]
@@ -209,6 +210,12 @@ def model_stats(model, G, L):
         branch_i = _stack_macs(ist("student")) + lin("student." + il)
         branch_a = _stack_macs(ast_("student")) + lin("student." + al)
         enc = branch_i + branch_a + lin("student.fusion.0") + lin("student.fusion.3")
+        if MIX_KIND.get(arch) == "xattn":
+            # per sample of a call of B samples: the four projections and, per direction, the
+            # Q K^T and P V products against the call's B keys (2 B E multiply-adds)
+            E = m.encoder_output_dim
+            enc += sum(lin(f"student.{a}.{p}") for a in XATTN_NAMES for p in ("q_proj", "kv_proj"))
+            enc += 2 * 2 * B * E
         macs = (G + L) * (enc + head("student_projection")) + G * (enc + head("teacher_projection"))
         heads = [k[:-len(".mlp.0.weight")] for k in spec if k.endswith(".mlp.0.weight")
                  and not k.startswith(("student_projection", "teacher_projection"))]
@@ -239,7 +246,7 @@ def write_run_summary(model, args, config, out, G, L, stats_cb, trainer, trainin
     if mlp:
         mlp_m, mlp_s = float(np.mean(mlp)), float(np.std(mlp))
     h = config["hyperparameters"]
-    gflops, params = model_stats(model, G, L)
+    gflops, params = model_stats(model, G, L, args.batch_size or h["batch_size"])
     name = config.get("model", {}).get("name") or (args.model or args.unimodal_model)
     cm = trainer.callback_metrics
     epoch_time, avg_batch = cm.get("epoch_time"), cm.get("avg_batch_time")
@@ -269,9 +276,13 @@ def write_run_summary(model, args, config, out, G, L, stats_cb, trainer, trainin
         "downstream_knn_accuracy": f"{knn_m:.4f}" if knn_m is not None else "N/A",
         "downstream_mlp_acc_std": f"{mlp_s:.4f}" if mlp_s is not None else "N/A",
         "downstream_knn_accuracy_std": f"{knn_s:.4f}" if knn_s is not None else "N/A",
-        # gate_image / gate_audio exist only on the gated encoders (not on the MI355X path)
         "final_audio_gate": "N/A", "final_image_gate": "N/A",
     }
+    # the learnable gates of the gated encoder (run_dino.py:454-465); "N/A" for every other model
+    store = model.model.store
+    if "student.gate_audio" in store.spec:
+        perf["final_audio_gate"] = store["student.gate_audio"].item()
+        perf["final_image_gate"] = store["student.gate_image"].item()
     with open(os.path.join(out, "performance_summary.txt"), "w") as f:
         for k, v in perf.items():
             f.write(f"{k}: {v}\n")

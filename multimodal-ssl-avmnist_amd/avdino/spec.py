@@ -6,6 +6,8 @@ checkpoints interoperate:
   image_encoder / audio_encoder   models/dino.py:18-73
   CentralMultiModalEncoder        models/dino.py:454-468 (fusion: 214-234)
   SimpleMultiModalEncoder         models/dino.py:214-234 (image_encoder / audio_encoder, 18-73)
+  GatedMultiModalEncoder          models/dino.py:237-259 (gate_image / gate_audio)
+  CrossAttentionMultiModalEncoder models/dino.py:407-452 (CrossModalAttention 385-404)
   ProjectionHead                  models/dino.py:1240-1254
   MultiModalDINO*                 models/dino.py:588-632, 964-970, 1053-1058, 1156-1161
   UniModalDINO / ImageEncoder     models/dino.py:1257-1297, 483-499
@@ -108,6 +110,30 @@ def simple_multimodal_sd(sd, prefix, E, D):
     _dense(sd, f"{prefix}.fusion.3", D, E)
 
 
+def gated_multimodal_sd(sd, prefix, E, D):
+    """GatedMultiModalEncoder (``--model multi_simple_gated``, dino.py:237-259): the two scalar
+    nn.Parameters are registered on the module itself, so they come before its submodules'
+    keys in the reference's state_dict."""
+    sd[f"{prefix}.gate_image"] = ((), "gate")
+    sd[f"{prefix}.gate_audio"] = ((), "gate")
+    simple_multimodal_sd(sd, prefix, E, D)
+
+
+def cross_attention_multimodal_sd(sd, prefix, E, D):
+    """CrossAttentionMultiModalEncoder (``--model multi_cross_attention``, dino.py:407-452):
+    the two CrossModalAttention modules (q_proj Linear(E,E), kv_proj Linear(E,2E), 385-391)
+    are created after fusion."""
+    simple_multimodal_sd(sd, prefix, E, D)
+    for att in XATTN_NAMES:
+        _dense(sd, f"{prefix}.{att}.q_proj", E, E)
+        _dense(sd, f"{prefix}.{att}.kv_proj", 2 * E, E)
+
+
+# the two attention directions: (queries from, keys / values from) the cat halves
+XATTN_NAMES = ("image_to_audio_attention", "audio_to_image_attention")
+GATE_INIT = 0.5             # nn.Parameter(torch.tensor(0.5)), dino.py:242-243
+
+
 # MODEL_MAP encoders that run on the engine (run_dino.py:530-540):
 #   arch -> (image stack(prefix), image Linear key, audio stack(prefix), audio Linear key, sd builder)
 MULTI_ENCODERS = {
@@ -117,7 +143,15 @@ MULTI_ENCODERS = {
     "multi_simple": (lambda p: cnn3_stack(f"{p}.image_encoder", CNN3_IMAGE_CONVS, 28), "image_encoder.14",
                      lambda p: cnn3_stack(f"{p}.audio_encoder", CNN3_AUDIO_CONVS, 112), "audio_encoder.18",
                      simple_multimodal_sd),
+    "multi_simple_gated": (lambda p: cnn3_stack(f"{p}.image_encoder", CNN3_IMAGE_CONVS, 28), "image_encoder.14",
+                           lambda p: cnn3_stack(f"{p}.audio_encoder", CNN3_AUDIO_CONVS, 112), "audio_encoder.18",
+                           gated_multimodal_sd),
+    "multi_cross_attention": (lambda p: cnn3_stack(f"{p}.image_encoder", CNN3_IMAGE_CONVS, 28), "image_encoder.14",
+                              lambda p: cnn3_stack(f"{p}.audio_encoder", CNN3_AUDIO_CONVS, 112),
+                              "audio_encoder.18", cross_attention_multimodal_sd),
 }
+# the stage between the cat of the two towers' features and fusion ("mix"): absent = plain cat
+MIX_KIND = {"multi_simple_gated": "gated", "multi_cross_attention": "xattn"}
 
 
 def projection_head_sd(sd, prefix, in_dim, out_dim, hidden=PROJ_HIDDEN):
