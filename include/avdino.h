@@ -176,6 +176,14 @@ int avd_linear_bwd_hwc(int rows, int O, int C, int HW, const float* dout, long l
  * conv -> BatchNorm2d(train) -> ReLU -> max_pool2d(2) block of CentralUnimodalImage /
  * CentralUnimodalAudio.forward (unimodal.py:127-221) and the 3x3 CNN blocks (dino.py:18-73),
  * forward and backward.  K in {3, 5}; Cin = 1 or a multiple of 8; Cout a multiple of 8.
+ * H and W are independent everywhere below: a rectangular map is either served (same results as
+ * the square-map contract) or declined -- the sizing query answers 0 or the entry point returns
+ * AVD_ERR_SHAPE before any launch (tests/test_gpu_rect.py pins which).  The routes measured for
+ * one exact map size (conv_ws.hip, wgrad_ws.hip, lbwd.hip, c1r5.hip, c1s3.hip, the MX kernels)
+ * need H and W both at that size; every other shape runs on the generic kernels.  One rule cuts
+ * across the generic ones: bf16 3x3 convs with Cin and Cout multiples of 32 (Cout <= 256) run on
+ * conv3.hip, which takes pad 1 and W <= 62 only (forward, and the input gradient of such a layer):
+ * AVD_ERR_SHAPE beyond, whatever avd_cl_stat_rows answered.
  *
  * Weights: wk = avd_cl_weight_layout(w [Cout,Cin,K,K] f32) in dt, dgrad=0 for the forward,
  * dgrad=1 (flipped taps, swapped channels) for the input gradient; avd_cl_weight_elems gives
@@ -246,8 +254,9 @@ int avd_cl_bn_bwd_apply(const void* y, int dt, const void* gout, int mode, const
 
 /* Fused BatchNorm-backward apply + conv weight gradient of a first (Cin = 1) layer whose output
  * is pooled in mode 0 -- the CentralNet audio conv1 (Cout 8, 5x5, pad 2, H, W % 16 == 0,
- * W <= 112) and the first 3x3 layer of the SimCLR / unimodal encoders (Cout 16/32, 3x3, pad 1,
- * H % 4 == 0, W even; models/dino.py:18-73), bf16: computes dy exactly as
+ * W <= 112) and the first 3x3 layer of the SimCLR / unimodal encoders (Cout 16/32/64, 3x3, pad 1,
+ * H % 4 == 0, W even, W <= 126 -- the staged rows' (4 + 2) * (W + 2) <= 768 -- and W <= 64 for
+ * Cout 64; models/dino.py:18-73), bf16; H and W independent in both.  Computes dy exactly as
  * avd_cl_bn_bwd_apply and, without storing it,
  * parts[s][Cout*K*K] = per-slab partial dW (reduce with avd_sum_rows over
  * avd_cl_apply_wgrad_slabs() rows).  Replaces avd_cl_bn_bwd_apply + avd_cl_conv_wgrad for that
@@ -382,10 +391,15 @@ int avd_cl_bn_bwd_reduce_pooled(const void* y, int dt, const void* pooled, const
  *                    dy = k1 dz + kx y + k0, so after avd_bn_bwd_finalize and avd_sum_rows of
  *                    the moments, avd_cl_c1_recompute_combine forms dW (y taken unrounded).
  * scale/shift/mean/invstd [G][Cout] from avd_bn_finalize, coef from avd_bn_bwd_finalize.
- * Shapes: Cin 1, bf16, the 5x5 pad-2 1->8 audio conv1 at 112^2 (CentralUnimodalAudio conv1+bn1+
- * pool, unimodal.py:160-190), and 1->16/32/64 3x3 pad 1 or 5x5 pad 2 with W % 4 == 0, W <= 128
- * (the 3x3 encoders' first layers, dino.py:18-73; CentralUnimodalImage conv1+bn1+pool,
- * unimodal.py:127-141); rows() == 0 otherwise. */
+ * Shapes: Cin 1, bf16, H and W independent:
+ *   - the 5x5 pad-2 1->8 audio conv1 (CentralUnimodalAudio conv1+bn1+pool, unimodal.py:160-190):
+ *     H % 16 == 0, W % 16 == 0, W <= 112;
+ *   - 3x3 pad 1, 1->16/32/64 (the 3x3 encoders' first layers, dino.py:18-73): H % 4 == 0,
+ *     W % 4 == 0 and W <= 128 (Cout 16), 120 (Cout 32), 72 (Cout 64) -- the 80 KB LDS bound of
+ *     passes 3 / 4; Cout 64 is not served at H == 28 with W <= 32 (whole-sample tiles, Cout <= 32);
+ *   - 5x5 pad 2, 1->32 only (CentralUnimodalImage conv1+bn1+pool, unimodal.py:127-141):
+ *     H % 4 == 0, W % 4 == 0, W <= 96.
+ * Every pass is served or none; rows() == 0 otherwise. */
 int avd_cl_c1_recompute_rows(int pass, int dt, int N, int B, int Cin, int H, int W, int Cout,
                              int K, int pad);
 int avd_cl_c1_recompute(int pass, const void* x, const void* wk, const float* bias,
@@ -645,7 +659,10 @@ int avd_adamw(float* p, const float* g, float* m, float* v, long long n, float l
  * avd_cl_c1_codes_combine (one launch, float64): the BN backward of bn1 (dgamma, dbeta, coef
  * [G][8][3] as avd_bn_bwd_finalize; sum dz y = w . M + b sum dz at the exact conv output), the
  * conv bias gradient dbias (= sum dy) and dW [8][25] = sum_g k1 M + kx (w Gram + b S) + k0 S.
- * count = B*H*W; coef / dgamma / dbeta / dbias nullable. */
+ * count = B*H*W; coef / dgamma / dbeta / dbias nullable.
+ * Served (these entry points and the avd_cl_c1_gram family below): H % 16 == 0, W % 16 == 0,
+ * W <= 112, H and W independent, N / B <= 32 BN groups; avd_cl_c1_codes_rows() == 0 and
+ * AVD_ERR_SHAPE otherwise. */
 int avd_cl_c1_codes_rows(int N, int B, int H, int W);
 int avd_cl_c1_codes_cols(void);
 int avd_cl_c1_apply_codes(const void* x, const void* wk, const float* bias, const float* scale,
@@ -780,8 +797,10 @@ int avd_cl_c1_codes_combine_gram(const float* moments, const float* gram, const 
                                  float* dbeta, float* dbias, float* coef, int G, void* stream);
 
 /* ------------------------------------------------------------------ routed 3x3 first layer
- * (28^2 and 112^2 run on the pixel-major / window-ordered kernels of c1s3.hip;
- * other shapes on c1w3.hip's recompute passes -- same contracts.)
+ * (28^2 and 112^2 -- H == W only -- run on the pixel-major / window-ordered kernels of c1s3.hip;
+ * other shapes on c1w3.hip's recompute passes -- same contracts.  Served: Cout 32, N / B <= 32 BN
+ * groups and the 3x3 Cout-32 rule of avd_cl_c1_recompute: H % 4 == 0, W % 4 == 0, W <= 120, H and
+ * W independent; avd_cl_c1r3_codes_rows() == 0 and AVD_ERR_SHAPE otherwise.)
  * The SimCLR / unimodal encoders' conv1 (audio_encoder / image_encoder, dino.py:18-73:
  * Conv2d(1, 32, 3, padding=1) -> BN2d -> ReLU -> MaxPool2d on 112x112 / 28x28, bf16) without a
  * stored conv output, backward routed by the forward's codes (the 3x3 counterpart of the
@@ -843,7 +862,10 @@ int avd_mx_conv_dgrad(const void* dy, const void* wq_d, const void* wsc_d, void*
                       int H, int W, int Cout, int K, int pad, void* stream);
 /* The conv's weight gradient (the autograd dW of nn.Conv2d) on the MX MFMA: x and dY bf16 NHWC
  * quantised while staged (one power-of-two scale per staged strip and operand), K = output
- * pixels; per-slab partials parts [avd_mx_wgrad_chunks][Cout][Cin][K][K] (sum: avd_sum_rows). */
+ * pixels; per-slab partials parts [avd_mx_wgrad_chunks][Cout][Cin][K][K] (sum: avd_sum_rows).
+ * Square maps only: avd_mx_wgrad_chunks takes H alone and answers for the H x H layer;
+ * avd_mx_conv_wgrad returns AVD_ERR_SHAPE for H != W before any launch.  The other MX queries
+ * (avd_mx_conv_serves / _ns, avd_mx_stat_rows) answer 0 unless H and W are both the served size. */
 int avd_mx_wgrad_chunks(int N, int Cin, int H, int Cout, int K, int pad);
 int avd_mx_conv_wgrad(const void* x, const void* dy, float* parts, int N, int Cin, int H, int W,
                       int Cout, int K, int pad, void* stream);
