@@ -509,14 +509,17 @@ int avd_l2norm_bwd(const float* y, const float* norms, const float* dy, float* d
  * this shard's first global row when the columns are all-gathered negatives); 2 = (r + R/2) % R
  * (NT-Xent positives over a local [2B] batch).  mask_off >= 0 excludes column r + mask_off
  * (NT-Xent self-similarity, multimodal_simclr.py:79-81); < 0 masks nothing.  col_major != 0
- * reads logits transposed (logits^T rows). */
+ * reads logits transposed (logits^T rows).  AVD_ERR_SHAPE unless ld (and ldd, with dlogits)
+ * spans a row (>= C; >= R when col_major), mode 1's last target R - 1 + tgt_off < C and, in
+ * mode 2, R <= C. */
 int avd_softmax_xent(const float* logits, long long ld, int R, int C, const int64_t* targets,
                      int target_mode, int tgt_off, int col_major, int mask_off, float gscale,
                      float* loss_parts, float* dlogits, long long ldd, int accumulate,
                      void* stream);
 
 /* correct[r] = 1.0f if argmax_j logits[r*ld + j] (first maximum, as torch.max) == targets[r],
- * else 0.0f -- the probe accuracy of evaluate() (dino.py:913-947). */
+ * else 0.0f -- the probe accuracy of evaluate() (dino.py:913-947).  A row of -inf predicts
+ * index 0, as avd_argmax_rows. */
 int avd_argmax_correct(const float* logits, long long ld, int R, int C, const int64_t* targets,
                        float* correct, void* stream);
 

@@ -287,12 +287,15 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(
   for (int j = l; j < C; j += 64)
     if (j != mcol) se += expf(logits[at(j)] - m);
   se = wave_sum(se);
-  const float lse = m + logf(se);
+  const float lg = logf(se);
+  const float lse = m + lg;
   if (l == 0) loss_parts[r] = lse - logits[at(tgt)];
   if (dlogits) {
+    // p_j = exp((x_j - m) - log se): the shifted logit is subtracted first, so p_j does not
+    // carry the rounding of lse at the row's magnitude (5e-4 relative for logits near 1e4)
     for (int j = l; j < C; j += 64) {
       float g = 0.f;
-      if (j != mcol) g = (expf(logits[at(j)] - lse) - (j == tgt ? 1.f : 0.f)) * gscale;
+      if (j != mcol) g = (expf((logits[at(j)] - m) - lg) - (j == tgt ? 1.f : 0.f)) * gscale;
       const size_t o = atd(j);
       dlogits[o] = accumulate ? dlogits[o] + g : g;
     }
@@ -375,7 +378,7 @@ __global__ __launch_bounds__(256) void argmax_correct_kernel(const float* __rest
   int bi = C;
   for (int j = l; j < C; j += 64) {
     const float v = logits[(size_t)r * ld + j];
-    if (v > best) { best = v; bi = j; }
+    if (v > best || bi == C) { best = v; bi = j; }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -445,6 +448,9 @@ int avd_softmax_xent(const float* logits, long long ld, int R, int C, const int6
   if (target_mode < 0 || target_mode > 2) return AVD_ERR_ARG;
   if (R <= 0 || C <= 0) return AVD_ERR_SHAPE;
   if (target_mode == 1 && (tgt_off < 0 || R - 1 + tgt_off >= C)) return AVD_ERR_SHAPE;
+  if (target_mode == 2 && R > C) return AVD_ERR_SHAPE;   // target (r + R/2) % R is a column
+  const int lmin = col_major ? R : C;                     // elements one leading step must span
+  if (ld < lmin || (dlogits && ldd < lmin)) return AVD_ERR_SHAPE;
   softmax_xent_kernel<<<avd_cdiv(R, 4), 256, 0, avd_stream(stream)>>>(
       logits, ld, R, C, targets, target_mode, tgt_off, col_major, mask_off, gscale, loss_parts,
       dlogits, ldd, accumulate);
