@@ -111,9 +111,10 @@ def test_gemm_modes_and_strides(ops, mode, shape):
     assert rel(host(C), ref) < tol
     # A^T and B^T storage (scalar / transposed staging paths), alpha / beta
     At, Bt = dev(A.T.copy()), dev(Bm.T.copy())
-    C2 = dev(np.ones((M, N), np.float32))
+    C_old = np.random.default_rng(11).normal(size=(M, N)).astype(np.float32)
+    C2 = dev(C_old)
     ops.gemm(M, N, K, At, 1, M, Bt, 1, K, C2, N, alpha=0.5, beta=2.0, mode=mode)
-    assert rel(host(C2), 0.5 * (A.astype(np.float64) @ Bm) + 2.0) < tol
+    assert rel(host(C2), 0.5 * (A.astype(np.float64) @ Bm) + 2.0 * C_old) < tol
     # column sums with a leading dimension and offset (Linear bias gradient)
     cs = torch.empty(N - 3, device="cuda")
     ops.sum_rows(dev(Bm), K, N - 3, cs, ld=N, off=3)
