@@ -622,6 +622,55 @@ int avd_augment_records(const float* stages, int nstages, int n, int H, int W, i
                         unsigned long long seed, float* rec, uint32_t* gm, int gm_words,
                         void* stream);
 
+/* SimCLR's image chain (SimCLRMultiModalAugmentation, get_data.py:299-408) adds two transforms
+ * that are not a function of one source pixel; the _x exports add them as stage kinds
+ *   9  elastic  ElasticTransform(alpha, sigma), bilinear, fill 0
+ *   10 blur     GaussianBlur(kernel_size K, sigma)
+ * with their per-record parameters in an extension ext[n, AVD_AUG_XREC] f32 beside the records
+ * (AVD_AUG_REC and its offsets are unchanged).  torchvision's published algorithms, restated
+ * (tests/simclr_aug_ref.py is the yardstick; parity with torchvision's own pixels is unpinned):
+ *   blur: w[i] = exp(-0.5 ((i - K/2) / sigma)^2) / sum, 2-D kernel outer(w, w), reflect padding
+ *     without edge repeat (-1 -> 1, H -> H-2), direct K x K sum; odd K in 3..7.
+ *   elastic: noise fields n_x, n_y = 2u - 1 per pixel, each smoothed by the same Gaussian with
+ *     K_e = int(8 sigma + 1) taps (+1 if even; rows then columns, reflect padding); the view is
+ *     sampled bilinearly with zero padding at
+ *       ix = x + b_x alpha W / (2H),  iy = y + b_y alpha H / (2W)
+ *     (torchvision scales dx by alpha / H and dy by alpha / W in normalised units;
+ *     grid_sample(align_corners=False) makes that d W/2 and d H/2 pixels) and multiplied by the
+ *     same bilinear sample of an all-ones map (img * mask + (1 - mask) * fill).
+ *     The uniform u for (record r, field f in {0: x, 1: y}, pixel p = y W + x) is
+ *       u = (mix64(seed ^ mix64(r << 32 | 0x80000000 | f << 16 | p)) >> 40) * 2^-24
+ *     with the kernel's counter hash mix64 (splitmix64's finaliser); GaussianNoise's counters
+ *     are pixel-pair indices < H*W/2 in the low word, so the two streams are disjoint.
+ * A chain with an elastic stage needs H*W <= 1024 (the fields and the row-pass temporaries live
+ * in the unused tail of the kernel's image buffer in LDS) and K_e/2 <= min(H, W) - 1 (reflect
+ * padding defined); a blur needs K/2 <= min(H, W) - 1.  A record whose own sigma / K breaks
+ * these limits has the stage skipped. */
+#define AVD_AUG_XREC 4
+enum {
+  AVD_AUG_XBLUR_SIGMA = 0, /* blur sigma; 0: the stage is off for this record */
+  AVD_AUG_XBLUR_K = 1,     /* blur kernel size */
+  AVD_AUG_XELA_ALPHA = 2,  /* elastic alpha; 0: off */
+  AVD_AUG_XELA_SIGMA = 3   /* elastic sigma */
+};
+/* avd_augment_views_seq with kinds 0..10, nkinds <= 11 and ext [B*V, AVD_AUG_XREC] (may be NULL
+ * without a kind 9 / 10).  A chain of kinds 0..8 gives avd_augment_views_seq's views bit for
+ * bit.  AVD_ERR_SHAPE: an elastic stage with H*W > 1024. */
+int avd_augment_views_x(const uint8_t* src_u8, const int64_t* idx, long long n_src, int B, int V,
+                        int H, int W, const float* lut, const float* rec, const uint32_t* gm,
+                        int gm_words, int group, unsigned long long seed, int order,
+                        const int* kinds, int nkinds, void* out, int odt, const float* ext,
+                        void* stream);
+/* avd_augment_records with nstages <= 11 and the two new kinds drawn into ext [n, AVD_AUG_XREC]
+ * (same stream: U < p first, then the stage's own draws, applied or not):
+ *   9 elastic {alpha, sigma} (no draw of its own), 10 blur {K, sigma_min, sigma_max} (one
+ *   uniform sigma for both axes).
+ * AVD_ERR_SHAPE: elastic with H*W > 1024 or K_e/2 > min(H, W) - 1; blur K even, outside 3..7
+ * or K/2 > min(H, W) - 1. */
+int avd_augment_records_x(const float* stages, int nstages, int n, int H, int W, int group,
+                          unsigned long long seed, float* rec, uint32_t* gm, int gm_words,
+                          float* ext, void* stream);
+
 /* ------------------------------------------------------------------ optimiser / EMA */
 
 /* teacher = m*teacher + (1-m)*student over n floats (MultiModalDINO.update_teacher,

@@ -122,6 +122,8 @@ PROTOS = {
     "avd_augment_views_nolds": [P, P, I, I, I, I, P, P, P, I, I, U64, I, P, P],
     "avd_augment_views_seq": [P, P, L, I, I, I, I, P, P, P, I, I, U64, I, P, I, P, I, P],
     "avd_augment_records": [P, I, I, I, I, I, U64, P, P, I, P],
+    "avd_augment_views_x": [P, P, L, I, I, I, I, P, P, P, I, I, U64, I, P, I, P, I, P, P],
+    "avd_augment_records_x": [P, I, I, I, I, I, U64, P, P, I, P, P],
     "avd_row_sqnorm": [P, I, I, P, P],
     "avd_knn_select": [P, L, P, I, I, I, P, P, I, P, I, P, P, P],
     "avd_argmax_rows": [P, L, I, I, P, P],

@@ -22,6 +22,14 @@ Transform chains (defaults, get_data.py:122-193) and how each stage is realised:
 * ``GaussianNoise(std)`` (get_data.py:21-27), ``GroupedMasking(ratio, 4)`` (get_data.py:60-108:
   exactly ``int(ratio * groups)`` distinct 4x4 groups zeroed).
 * ``RandomApply([t], p)`` -- applied when U < p.
+* ``ElasticTransform(alpha, sigma)`` / ``GaussianBlur(kernel_size, sigma=(lo, hi))`` -- the SimCLR
+  image chain's two extra stages (``simclr_chains``, get_data.py:313-339).  Neither is a function
+  of one source pixel, so they exist only in the stage-by-stage kernel, behind the ``_x`` exports
+  (``avd_augment_views_x`` / ``avd_augment_records_x``), with their per-record parameters in an
+  extension ``ext [n, XREC]`` beside the records: blur = direct K x K Gaussian over the
+  reflect-padded view; elastic = two counter-hash noise fields smoothed by a
+  ``int(8 sigma + 1)``-tap Gaussian, then a zero-padded bilinear resample times the same
+  resample of an all-ones mask (fill 0).  Elastic needs H*W <= 1024 (include/avdino.h).
 
 The random streams are numpy's, not torch's global generator, so individual views are not the
 reference's views (the reference's own views are not reproducible across worker counts); the
@@ -40,6 +48,9 @@ from . import ops
 KIND_ORDER = {"crop": 0, "time_warp": 1, "frequency_mask": 2, "time_mask": 2, "rotation": 3,
               "affine": 4, "erasing": 5, "gaussian_noise": 6, "grouped_masking": 7}
 REC = ops.AUG_REC
+XREC = ops.AUG_XREC       # ext record: blur sigma, blur K, elastic alpha, elastic sigma
+X_KINDS = ("elastic", "blur")
+_X_PARAMS = {"elastic": ("alpha", "sigma"), "blur": ("kernel_size", "sigma")}
 F_CROP, F_AFF, F_ROT, F_TW = 1, 2, 4, 8
 
 
@@ -82,20 +93,75 @@ def custom_audio_chain(augmentations, probabilities):
     return chain
 
 
-def validate_chain(chain):
+def simclr_chains():
+    """SimCLRMultiModalAugmentation's default chains (get_data.py:313-369)."""
+    image = [("crop", dict(scale=(0.5, 1.0), ratio=(0.8, 1.2)), 1.0),
+             ("rotation", dict(degrees=5), 1.0),
+             ("affine", dict(translate=(0.1, 0.1)), 1.0),
+             ("elastic", dict(alpha=20.0, sigma=3.0), 0.3),
+             ("blur", dict(kernel_size=3, sigma=(0.1, 0.5)), 0.3)]
+    audio = [("crop", dict(scale=(0.5, 1.0)), 1.0),
+             ("time_warp", dict(min_factor=0.9, max_factor=1.1), 0.5),
+             ("frequency_mask", dict(freq_mask_param=10), 0.5),
+             ("time_mask", dict(time_mask_param=10), 0.5),
+             ("gaussian_noise", dict(std=0.05), 0.3)]
+    return {"image": image, "audio": audio}
+
+
+def elastic_taps(sigma):
+    """ElasticTransform's Gaussian kernel size int(8 sigma + 1), made odd; float32 like the
+    kernel (csrc/augment.hip elastic_taps)."""
+    ke = int(np.float32(8.0) * np.float32(sigma) + np.float32(1.0))
+    return ke if ke & 1 else ke + 1
+
+
+def _blur_params(kw):
+    K, sg = kw["kernel_size"], kw["sigma"]
+    lo, hi = (sg, sg) if np.isscalar(sg) else sg
+    if int(K) != K or K % 2 == 0 or not 3 <= K <= 7:
+        raise ValueError("blur kernel_size must be odd, 3..7")
+    if not 0 < lo <= hi:
+        raise ValueError("blur sigma must satisfy 0 < min <= max")
+    return int(K), float(lo), float(hi)
+
+
+def has_x(chain):
+    """True when the chain holds an elastic or blur stage (the ``_x`` exports)."""
+    return any(kind in X_KINDS for kind, _, _ in chain)
+
+
+def validate_chain(chain, H=None, W=None):
     """Every stage a known transform, each at most once (a record has one parameter slot per
-    transform kind).  Any order: transforms.Compose order is kept (avd_augment_views_seq)."""
+    transform kind).  Any order: transforms.Compose order is kept (avd_augment_views_seq).
+    The elastic and blur stages take their parameters spelled out (``alpha`` and ``sigma``;
+    ``kernel_size`` and ``sigma``) -- a stage without them is not supported; with the map size,
+    their size limits are checked too (include/avdino.h)."""
     seen = set()
-    for kind, _, _ in chain:
-        if kind not in KIND_ORDER or kind in seen:
+    for kind, kw, _ in chain:
+        if (kind not in KIND_ORDER and kind not in X_KINDS) or kind in seen:
             raise NotImplementedError(f"transform chain not supported on device: {chain}")
         seen.add(kind)
+        if kind in X_KINDS and not set(_X_PARAMS[kind]) <= set(kw):
+            raise NotImplementedError(f"device {kind} stage needs {_X_PARAMS[kind]}: {chain}")
+        if kind == "blur":
+            K, _lo, _hi = _blur_params(kw)
+            if H is not None and K // 2 > min(H, W) - 1:
+                raise ValueError("blur kernel larger than the map's reflect padding allows")
+        elif kind == "elastic":
+            if not kw["sigma"] > 0:
+                raise ValueError("elastic sigma must be positive")
+            if H is not None and (H * W > ops.AUG_MAX_ELASTIC_HW or
+                                  elastic_taps(kw["sigma"]) // 2 > min(H, W) - 1):
+                raise ValueError("elastic stage needs H*W <= 1024 and K_e/2 <= min(H, W) - 1")
 
 
 def fixed_order(chain):
     """True when the chain is a sub-sequence of the gather kernel's order (avd_augment_views:
     crop -> time stretch -> masks -> rotation -> affine -> erasing -> noise -> groups), so the
-    one-pass gather kernel applies it; other orders run stage by stage (avd_augment_views_seq)."""
+    one-pass gather kernel applies it; other orders run stage by stage (avd_augment_views_seq).
+    A chain with an elastic or blur stage is never fixed-order (avd_augment_views_x)."""
+    if has_x(chain):
+        return False
     last = -1
     for kind, _, _ in chain:
         if KIND_ORDER[kind] < last:
@@ -183,9 +249,18 @@ def _group_bits(rng, n, ng, k):
 
 
 def sample_records(rng, chain, n, H, W, group=4):
-    """Draw one view's parameters for n samples: (rec [n, REC] f32, gm bitmask rows or None)."""
-    validate_chain(chain)
+    """Draw one view's parameters for n samples: (rec [n, REC] f32, gm bitmask rows or None).
+    Chains with an elastic / blur stage: sample_records_x."""
+    if has_x(chain):
+        raise NotImplementedError("elastic / blur stages draw an ext record: sample_records_x")
+    return sample_records_x(rng, chain, n, H, W, group)[:2]
+
+
+def sample_records_x(rng, chain, n, H, W, group=4):
+    """sample_records plus the elastic / blur extension: (rec, gm, ext [n, XREC] f32)."""
+    validate_chain(chain, H, W)
     rec = np.zeros((n, REC), np.float32)
+    ext = np.zeros((n, XREC), np.float32)
     rec[:, 22] = -1
     flags = np.zeros(n, np.int64)
     gm = None
@@ -233,19 +308,27 @@ def sample_records(rng, chain, n, H, W, group=4):
             ng = (H // g) * (W // g)
             gm = _group_bits(rng, n, ng, int(kw.get("mask_ratio", 0.5) * ng))
             rec[on, 22] = np.arange(n)[on]
+        elif kind == "elastic":     # fixed parameters; the view kernel draws the fields
+            ext[on, 2], ext[on, 3] = kw["alpha"], kw["sigma"]
+        elif kind == "blur":        # GaussianBlur.get_params: one sigma for both axes
+            K, lo, hi = _blur_params(kw)
+            sigma = rng.uniform(lo, hi, n)
+            ext[on, 0], ext[on, 1] = sigma[on], K
     rec[:, 23] = flags
-    return rec, gm
+    return rec, gm, ext
 
 
 # ----------------------------------------------------------------------------- device draws
 _SK = {"crop": 0, "time_warp": 1, "frequency_mask": 2, "time_mask": 3, "rotation": 4,
-       "affine": 5, "erasing": 6, "gaussian_noise": 7, "grouped_masking": 8}
+       "affine": 5, "erasing": 6, "gaussian_noise": 7, "grouped_masking": 8,
+       "elastic": ops.AUG_SK_ELASTIC, "blur": ops.AUG_SK_BLUR}
 
 
-def chain_stages(chain, group=4):
+def chain_stages(chain, group=4, H=None, W=None):
     """A chain as avd_augment_records' host stage table [S, 8] f32: {kind, p, params...}
-    (include/avdino.h)."""
-    validate_chain(chain)
+    (include/avdino.h; elastic {alpha, sigma} and blur {K, sigma_min, sigma_max} for
+    avd_augment_records_x)."""
+    validate_chain(chain, H, W)
     st = np.zeros((len(chain), ops.AUG_STAGE_F), np.float32)
     for i, (kind, kw, pr) in enumerate(chain):
         q = st[i, 2:]
@@ -275,6 +358,10 @@ def chain_stages(chain, group=4):
             if kw.get("group_size", 4) != group:
                 raise ValueError("grouped masking group size must match the kernel's group")
             q[0] = kw.get("mask_ratio", 0.5)
+        elif kind == "elastic":
+            q[0], q[1] = kw["alpha"], kw["sigma"]
+        elif kind == "blur":
+            q[0:3] = _blur_params(kw)
     return st
 
 
@@ -299,11 +386,12 @@ class ViewAugmenter:
         self._pinned = collections.deque(maxlen=64)    # host ids of in-flight transfers
 
     def records_dev(self, chain, B, n_views, group=4):
-        """(rec [B*n_views, REC], gm [B*n_views, words] or None) drawn on the device."""
+        """(rec [B*n_views, REC], gm [B*n_views, words] or None) drawn on the device; with an
+        elastic / blur stage in the chain also ext [B*n_views, XREC] (avd_augment_records_x)."""
         key = id(chain)
         st = self._stage_cache.get(key)
         if st is None or st[0] is not chain:
-            st = (chain, chain_stages(chain, group))
+            st = (chain, chain_stages(chain, group, self.H, self.W))
             self._stage_cache[key] = st
         stages = st[1]
         n = B * n_views
@@ -315,33 +403,39 @@ class ViewAugmenter:
             gm = torch.empty(n, words, dtype=torch.int32, device=dev)
         self.calls += 1
         rseed = (self.seed * 0xD1B54A32D192ED03 + 0x5EED * self.calls) & (2**64 - 1)
+        if has_x(chain):
+            ext = torch.empty(n, XREC, dtype=torch.float32, device=dev)
+            ops.augment_records_x(stages, n, self.H, self.W, group, rseed, rec, gm, ext)
+            return rec, gm, ext
         ops.augment_records(stages, n, self.H, self.W, group, rseed, rec, gm)
         return rec, gm
 
     def records(self, chain, B, n_views):
+        """Host (numpy) draws: (rec, gm), and ext too for a chain with an elastic / blur stage."""
         rec = np.zeros((B, n_views, REC), np.float32)
+        ext = np.zeros((B, n_views, XREC), np.float32)
         gms, rows = [], 0
         for v in range(n_views):
-            r, gm = sample_records(self.rng, chain, B, self.H, self.W)
+            r, gm, ext[:, v] = sample_records_x(self.rng, chain, B, self.H, self.W)
             if gm is not None:
                 r[r[:, 22] >= 0, 22] += rows
                 gms.append(gm)
                 rows += gm.shape[0]
             rec[:, v] = r
-        return rec.reshape(B * n_views, REC), (np.concatenate(gms) if gms else None)
+        out = rec.reshape(B * n_views, REC), (np.concatenate(gms) if gms else None)
+        return out + (ext.reshape(B * n_views, XREC),) if has_x(chain) else out
 
     def __call__(self, idx, chain, n_views, out=None, order=0):
         idx = np.asarray(idx, np.int64)
-        if self.device_params:
-            rec, gm = self.records_dev(chain, idx.shape[0], n_views)
-        else:
-            rec, gm = self.records(chain, idx.shape[0], n_views)
+        draw = self.records_dev if self.device_params else self.records
+        rec, gm, *ext = draw(chain, idx.shape[0], n_views)
         kinds = chain_kinds(chain) if (self.sequential or not fixed_order(chain)) else None
-        return self.apply(idx, rec, gm, n_views, out, order, kinds)
+        return self.apply(idx, rec, gm, n_views, out, order, kinds, *ext)
 
-    def apply(self, idx, rec, gm, n_views, out=None, order=0, kinds=None):
+    def apply(self, idx, rec, gm, n_views, out=None, order=0, kinds=None, ext=None):
         """kinds: the stage kinds in application order for avd_augment_views_seq (None: the
-        fixed-order gather kernel)."""
+        fixed-order gather kernel); ext [B*n_views, XREC]: the elastic / blur parameters of a
+        chain that has those kinds (avd_augment_views_x)."""
         idx = np.asarray(idx, np.int64)
         if idx.size == 0 or idx.min() < 0 or idx.max() >= self.src.shape[0]:
             raise IndexError("sample id outside the dataset")
@@ -370,6 +464,11 @@ class ViewAugmenter:
             gm_d = None if gm is None else torch.from_numpy(gm.view(np.int32)).to(dev)
         self.calls += 1
         seed = (self.seed * 0x9E3779B97F4A7C15 + self.calls) & (2**64 - 1)
+        if ext is not None:
+            ext_d = ext if on_dev else torch.from_numpy(np.ascontiguousarray(ext, np.float32)).to(dev)
+            ops.augment_views_x(self.src, idx_d, self.lut, rec_d, gm_d, 4, seed, n_views, self.H,
+                                self.W, out, order, kinds, ext_d)
+            return out
         ops.augment_views(self.src, idx_d, self.lut, rec_d, gm_d, 4, seed, n_views, self.H,
                           self.W, out, order, kinds)
         return out
@@ -435,6 +534,46 @@ class MultiModalAugmentation:
                 aug(idx, self.local_transforms[key], L, out=xv[G:G + L].view(-1), order=1)
             if with_orig:
                 aug.identity(idx, out=xv[G + L].view(-1))
+
+
+class SimCLRMultiModalAugmentation:
+    """Device counterpart of get_data.py:299-408: two independently drawn views per modality.
+
+    Same constructor; after ``bind(image_augmenter, audio_augmenter)``, ``__call__(idx)`` returns
+    ``(aug_images1, aug_audios1, aug_images2, aug_audios2)``, each f32 [B, 1, H, W] on the device
+    (the reference calls each transform twice per sample; here the two views of a modality come
+    from one launch with two records per sample).
+
+    ``augment_values``: the reference builds a custom audio chain from it and then never uses it
+    (get_data.py:371-390 -- ``audio_augs`` is dropped, the default transforms are assigned), so
+    the argument is accepted, its names are checked, and the default chains stay."""
+
+    _CUSTOM_AUDIO = ("time_warp", "frequency_mask", "time_mask", "grouped_masking",
+                     "gaussian_noise")
+
+    def __init__(self, image_size=28, spec_size=112, augment_values=None):
+        if image_size != 28 or spec_size != 112:
+            raise NotImplementedError("device crops resize to the stored 28x28 / 112x112 maps")
+        self.image_size, self.spec_size = image_size, spec_size
+        if augment_values is not None:
+            for name in augment_values["augmentations"]:
+                if name not in self._CUSTOM_AUDIO:
+                    raise KeyError(name)
+                augment_values["augmentation_probabilities"][name]
+        ch = simclr_chains()
+        self.image_transform, self.spectrogram_transform = ch["image"], ch["audio"]
+        validate_chain(self.image_transform, image_size, image_size)
+        validate_chain(self.spectrogram_transform, spec_size, spec_size)
+        self.image = self.audio = None
+
+    def bind(self, image_aug, audio_aug):
+        self.image, self.audio = image_aug, audio_aug
+        return self
+
+    def __call__(self, idx):
+        img = self.image(idx, self.image_transform, 2, order=1)          # [2, B, 1, H, W]
+        aud = self.audio(idx, self.spectrogram_transform, 2, order=1)
+        return img[0], aud[0], img[1], aud[1]
 
 
 def process_augment_config(config, trial=None, is_hyperparameter_search=False):

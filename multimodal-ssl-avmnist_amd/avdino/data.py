@@ -1,7 +1,7 @@
 """AVMNIST on-disk loader with the dataset resident in HBM.
 
 Reference: ``BaseAVMNISTDataset`` / ``AVMNISTDataset`` / ``AVMNISTSSLDataset(Extended)`` and the
-data modules in AVMNIST_Experiments/utils/get_data.py:412-672, ``MemmapWrapper`` 745-764.
+data modules in AVMNIST_Experiments/utils/get_data.py:412-741, ``MemmapWrapper`` 745-764.
 
 File contract (unchanged, so an existing AVMNIST directory drops in):
 
@@ -26,7 +26,7 @@ import os
 import numpy as np
 import torch
 
-from .augment import MultiModalAugmentation, ViewAugmenter
+from .augment import MultiModalAugmentation, SimCLRMultiModalAugmentation, ViewAugmenter
 
 IMG_HW, AUD_HW = (28, 28), (112, 112)
 
@@ -234,3 +234,78 @@ class AVMNISTLabelledLoader:
             b = idx[s:s + self.batch_size]
             lab = self.dev["labels"][torch.from_numpy(np.asarray(b, np.int64)).to(self.dev["labels"].device)]
             yield self.image.identity(b), self.audio.identity(b), lab
+
+
+class _SimCLRViewLoader:
+    """One split of AVMNISTSimCLRDataModule: batches of (img1, spec1, img2, spec2)."""
+
+    def __init__(self, module, idx, shuffle):
+        self.m, self.idx, self.shuffle, self.epoch = module, idx, shuffle, 0
+
+    def __len__(self):
+        return -(-len(self.idx) // self.m.batch_size)
+
+    def __iter__(self):
+        idx = self.idx
+        if self.shuffle:   # a fresh permutation per epoch, as AVMNISTDinoLoader._order
+            g = torch.Generator().manual_seed(self.m.seed + 1000003 * (self.epoch + 1))
+            idx = idx[torch.randperm(len(idx), generator=g).numpy()]
+        self.epoch += 1
+        for s in range(0, len(idx), self.m.batch_size):
+            yield self.m.augmentations(idx[s:s + self.m.batch_size])
+
+
+class AVMNISTSimCLRDataModule:
+    """``AVMNISTSimCLRDataModule`` (get_data.py:708-741) with the dataset resident in HBM and the
+    views built on the device (SimCLRMultiModalAugmentation: one launch per modality per batch, on
+    the current stream between steps).
+
+    ``train_dataloader()`` / ``val_dataloader()`` iterate the two parts of
+    ``random_split(train, [train_size, val_size])`` and yield ``(aug_images1, aug_audios1,
+    aug_images2, aug_audios2)``, each f32 [B, 1, H, W]; train shuffles per epoch.
+    ``test_dataloader()`` yields un-augmented ``(image, audio, label)`` from the test files
+    (AVMNISTLabelledLoader).  ``num_workers`` is accepted for signature parity and unused."""
+
+    def __init__(self, data_dir, batch_size=128, num_workers=6, type="burst_noise",
+                 augmentations=None, device="cuda", seed=0, train_size=55000, val_size=5000):
+        self.data_dir, self.batch_size, self.num_workers, self.type = data_dir, batch_size, num_workers, type
+        self.device, self.seed = device, seed
+        self.train_size, self.val_size = train_size, val_size
+        self.augmentations = SimCLRMultiModalAugmentation() if augmentations is None else augmentations
+        self.train_idx = self.val_idx = self._test = None
+
+    def prepare_data(self):
+        prepare_data(self.data_dir, self.type)
+
+    def setup(self, stage=None):
+        if stage in ("fit", None) and self.train_idx is None:
+            paths = avmnist_paths(self.data_dir, self.type)["train"]
+            for path in paths:
+                if not os.path.exists(path):
+                    raise FileNotFoundError(f"Data file not found: {path}")
+            arrays = AVMNISTArrays(*paths)
+            self.dev = arrays.to_device(self.device)
+            gen = torch.Generator().manual_seed(self.seed)
+            self.train_idx, self.val_idx = random_split_indices(
+                len(arrays), [self.train_size, self.val_size], gen)
+            self.augmentations.bind(
+                ViewAugmenter(self.dev["image"], self.dev["lut_image"], *IMG_HW, seed=self.seed),
+                ViewAugmenter(self.dev["audio"], self.dev["lut_audio"], *AUD_HW, seed=self.seed + 1))
+        if stage in ("test", None) and self._test is None:
+            self._test = AVMNISTLabelledLoader(self.data_dir, self.batch_size, self.type,
+                                               self.device, split="test", seed=self.seed)
+
+    def train_dataloader(self):
+        if self.train_idx is None:
+            self.setup("fit")
+        return _SimCLRViewLoader(self, self.train_idx, True)
+
+    def val_dataloader(self):
+        if self.train_idx is None:
+            self.setup("fit")
+        return _SimCLRViewLoader(self, self.val_idx, False)
+
+    def test_dataloader(self):
+        if self._test is None:
+            self.setup("test")
+        return self._test

@@ -1325,6 +1325,60 @@ def augment_records(stages, n, H, W, group, seed, rec, gm):
          p(rec), p(gm), words, stream())
 
 
+# the elastic / blur stages (avd_augment_views_x, avd_augment_records_x; include/avdino.h)
+AUG_XREC = 4             # floats per record extension: blur sigma, blur K, elastic alpha, sigma
+AUG_MAX_STAGES_X = 11
+AUG_SK_ELASTIC, AUG_SK_BLUR = 9, 10
+AUG_MAX_ELASTIC_HW = 1024
+
+
+def augment_views_x(src_u8, idx, lut, rec, gm, group, seed, V, H, W, out, order, kinds, ext):
+    """augment_views' stage-by-stage path with the elastic (9) and blur (10) kinds
+    (avd_augment_views_x): ``ext`` f32 [B*V, AUG_XREC] on the device holds their per-record
+    parameters (None only for a chain without them)."""
+    import numpy as _np
+    B = idx.numel()
+    _need(src_u8.dtype == torch.uint8 and src_u8.dim() == 2 and src_u8.shape[1] == H * W, "aug src")
+    _need(idx.dtype == torch.int64 and lut.numel() == 256 and lut.dtype == torch.float32, "aug idx/lut")
+    _need(rec.dtype == torch.float32 and rec.shape == (B * V, AUG_REC), "aug records")
+    _need(out.dtype in (torch.float32, torch.bfloat16) and out.numel() == B * V * H * W, "aug out")
+    ks = _np.ascontiguousarray(kinds, _np.int32)
+    _need(ks.ndim == 1 and ks.shape[0] <= AUG_MAX_STAGES_X, "aug stage kinds")
+    new = bool(((ks == AUG_SK_ELASTIC) | (ks == AUG_SK_BLUR)).any())
+    _need(ext is not None or not new, "aug ext missing for an elastic / blur stage")
+    if ext is not None:
+        _need(ext.dtype == torch.float32, "aug ext dtype")
+        _need(ext.numel() == B * V * AUG_XREC, "aug ext numel")
+    _need(not (ks == AUG_SK_ELASTIC).any() or H * W <= AUG_MAX_ELASTIC_HW,
+          "elastic stage needs H*W <= 1024")
+    for t in (src_u8, idx, lut, rec, out) + tuple(x for x in (gm, ext) if x is not None):
+        _need(t.is_contiguous() and t.device == out.device, "aug operands contiguous, one device")
+    words = gm.shape[1] if gm is not None else 0
+    call("avd_augment_views_x", p(src_u8), p(idx), src_u8.shape[0], B, V, H, W, p(lut), p(rec),
+         p(gm), words, group, seed & (2**64 - 1), order, ks.ctypes.data, ks.shape[0], p(out),
+         dtcode(out), p(ext), stream())
+
+
+def augment_records_x(stages, n, H, W, group, seed, rec, gm, ext):
+    """augment_records with the elastic / blur kinds drawn into ``ext`` f32 [n, AUG_XREC]
+    (avd_augment_records_x)."""
+    import numpy as _np
+    st = _np.ascontiguousarray(stages, _np.float32)
+    _need(st.ndim == 2 and st.shape[1] == AUG_STAGE_F and st.shape[0] <= AUG_MAX_STAGES_X, "aug stages")
+    _need(rec.dtype == torch.float32 and rec.shape == (n, AUG_REC) and rec.is_contiguous(), "aug rec out")
+    _need(ext is not None and ext.dtype == torch.float32, "aug ext dtype")
+    _need(ext.numel() == n * AUG_XREC and ext.is_contiguous() and ext.device == rec.device,
+          "aug ext numel")
+    _need(not (st[:, 0] == AUG_SK_ELASTIC).any() or H * W <= AUG_MAX_ELASTIC_HW,
+          "elastic stage needs H*W <= 1024")
+    words = 0
+    if gm is not None:
+        _need(gm.dim() == 2 and gm.shape[0] == n and gm.is_contiguous(), "aug gm out")
+        words = gm.shape[1]
+    call("avd_augment_records_x", st.ctypes.data, st.shape[0], n, H, W, group, seed & (2**64 - 1),
+         p(rec), p(gm), words, p(ext), stream())
+
+
 # ---------------------------------------------------------------- timeline marks (tools)
 class Marks:
     """Phase marks of a step (avd_mark): ``mark(name)`` records the device real-time counter

@@ -18,9 +18,8 @@ and ``training_structures/ssl_train.py`` (the SimCLR experiment, BASELINE config
   LateFusionEncoder             ssl_train.py:245-292   concat / sum / mean of the two towers
   evaluate_multimodal_ssl       ssl_train.py:294-359   late-fusion accuracies over checkpoints
 
-Out of scope there: the plots (visualize_results: PCA, t-SNE, confusion figures, loss curves)
-and the SimCLR augmentation data module (AVMNISTSimCLRDataModule with its rotation / elastic /
-time-warp transforms) -- the drivers take whatever data modules the caller passes.
+Out of scope there: the plots (visualize_results: PCA, t-SNE, confusion figures, loss curves).
+The SimCLR augmentation data module is avdino.data.AVMNISTSimCLRDataModule.
 
 Deviation, documented: the reference's pretrain_dino unpacks ``student_out, teacher_out =
 model(batch)``, while its current models return three values (dino.py:727, 1398) and would
@@ -214,8 +213,8 @@ def train_and_evaluate_ssl(module, train_data_module, test_data_module, model_di
     ``val_dataloader()``, ``test_dataloader()`` yielding (image, audio, label).  ``input_data``
     is accepted for signature parity and unused: parameters / gflops come from ssl_model_stats
     (gflops analytic, not pinned to the reference's profiler figure).  Returns the summary dict
-    (``per_seed`` added: the per-seed accuracies).  Not mirrored: the plots and the SimCLR
-    augmentation data module (module docstring)."""
+    (``per_seed`` added: the per-seed accuracies).  Not mirrored: the plots (module
+    docstring)."""
     import copy
     import time
 

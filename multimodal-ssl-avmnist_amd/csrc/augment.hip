@@ -240,8 +240,57 @@ __global__ __launch_bounds__(kThreads) void augment_kernel(
   }
 }
 
-enum { SK_CROP = 0, SK_TWARP, SK_FMASK, SK_TMASK, SK_ROT, SK_AFF, SK_ERASE, SK_NOISE, SK_GMASK };
+enum { SK_CROP = 0, SK_TWARP, SK_FMASK, SK_TMASK, SK_ROT, SK_AFF, SK_ERASE, SK_NOISE, SK_GMASK,
+       SK_ELASTIC, SK_BLUR };
 constexpr int kMaxStages = 9, kStageF = 8, kMaxGroups = 1024;
+// the _x exports (kinds up to SK_BLUR): stage limit, the largest map an elastic stage takes (its
+// two displacement fields and their row-pass temporaries live in the image buffer's tail) and
+// the blur kernel sizes
+constexpr int kMaxStagesX = 11, kMaxElasticHW = 1024, kMinBlurK = 3, kMaxBlurK = 7;
+
+// ElasticTransform's Gaussian kernel size for a sigma: int(8 sigma + 1), made odd
+__host__ __device__ __forceinline__ int elastic_taps(float sigma) {
+  const int ke = (int)(8.0f * sigma + 1.0f);
+  return (ke & 1) ? ke : ke + 1;
+}
+
+// torch's reflect padding (no edge repeat): -1 -> 1, n -> n - 2; defined for |offset| <= n - 1
+__device__ __forceinline__ int reflect(int i, int n) {
+  return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i);
+}
+
+// The elastic stage's uniform draw for (record, field, pixel): the counter hash of Urng::u and
+// gauss2 with the low key word 0x80000000 | field << 16 | pixel (field 0 = x, 1 = y; pixel <
+// 1024) -- gauss2's low words are pixel-pair indices < H*W/2 < 2^31, so the two never meet:
+//   r = mix64(seed ^ mix64(rec << 32 | 0x80000000 | field << 16 | pixel)),  u = (r >> 40) * 2^-24
+// and the noise value is 2u - 1 (exact in f32).
+__device__ __forceinline__ float elastic_noise(unsigned long long seed, unsigned rec, unsigned field,
+                                               unsigned pix) {
+#pragma clang fp contract(off)
+  const unsigned low = 0x80000000u | (field << 16) | pix;
+  const unsigned long long r = mix64(seed ^ mix64(((unsigned long long)rec << 32) | low));
+  return 2.0f * ((float)(r >> 40) * 5.9604644775390625e-8f) - 1.0f;
+}
+
+// The normalised 1-D Gaussian w[i] = exp(-0.5 ((i - K/2) / sigma)^2) / sum into LDS (K <= 256
+// taps, summed in index order).  Called by the whole block; ends with a barrier.
+__device__ __forceinline__ void gauss_taps(float* s_w, int K, float sigma) {
+#pragma clang fp contract(off)
+  const int t = threadIdx.x;
+  float e = 0.0f;
+  if (t < K) {
+    const float x = (float)(t - K / 2) / sigma;
+    e = expf(-0.5f * (x * x));
+    s_w[t] = e;
+  }
+  __syncthreads();
+  float sum = 0.0f;
+  if (t < K)
+    for (int i = 0; i < K; ++i) sum = sum + s_w[i];
+  __syncthreads();
+  if (t < K) s_w[t] = e / sum;
+  __syncthreads();
+}
 
 // ----------------------------------------------------------------------------- any stage order
 // transforms.Compose applies a chain in its own order, and the reference's own config
@@ -255,13 +304,22 @@ constexpr int kMaxStages = 9, kStageF = 8, kMaxGroups = 1024;
 // barrier, then overwrite the image; the value stages (masks, erasing, noise, groups) update
 // their own pixels in place.  Same per-pixel formulas as the gather kernel, so a chain in the
 // fixed order gives bit-identical views either way.
-struct Prog { int kind[kMaxStages]; int n; };
+struct Prog { int kind[kMaxStagesX]; int n; };
 
-template <typename TO, int NPT>
+//
+// X (the _x exports) adds the two stages that are not a function of one source pixel: SK_BLUR, a
+// direct K x K Gaussian over the reflect-padded view (a gather stage), and SK_ELASTIC, which
+// draws two noise fields, smooths each with a separable Gaussian (rows, then columns) and
+// resamples the view bilinearly at the displaced positions.  Their parameters come from the
+// record's extension ext[AVD_AUG_XREC].  The tap weights reuse the byte table's LDS (the table is
+// dead once the row is staged); the elastic fields and row-pass temporaries sit in the image
+// buffer's tail s_img[H*W ..] (H*W <= 1024), so static LDS is what it was.
+template <typename TO, int NPT, bool X = false>
 __global__ __launch_bounds__(kThreads) void augment_seq_kernel(
     const uint8_t* __restrict__ src, const int64_t* __restrict__ idx, int V, int B, int H, int W,
     const float* __restrict__ lut, const float* __restrict__ recs, const uint32_t* __restrict__ gm,
-    int gm_words, int group, unsigned long long seed, int order, Prog prog, TO* __restrict__ out) {
+    int gm_words, int group, unsigned long long seed, int order, Prog prog, TO* __restrict__ out,
+    const float* __restrict__ ext = nullptr) {
 #pragma clang fp contract(off)
   __shared__ float s_img[kMaxHW];
   __shared__ float s_lut[256];
@@ -381,6 +439,107 @@ __global__ __launch_bounds__(kThreads) void augment_seq_kernel(
         const int g = (y / group) * gw + x / group;
         if ((gmr[g >> 5] >> (g & 31)) & 1u) s_img[p] = s_img[p] * 0.0f;
       }
+    } else if (X && kind == SK_BLUR) {
+      const float* xr = ext + (size_t)rid * AVD_AUG_XREC;
+      const float sigma = xr[AVD_AUG_XBLUR_SIGMA];
+      const int K = (int)xr[AVD_AUG_XBLUR_K];
+      // off, or a size the host checks would have refused (records built elsewhere)
+      if (!(sigma > 0.0f) || K < kMinBlurK || K > kMaxBlurK || !(K & 1) || K / 2 > H - 1 ||
+          K / 2 > W - 1)
+        continue;
+      gauss_taps(s_lut, K, sigma);
+      const int r = K / 2;
+#pragma unroll
+      for (int k = 0; k < NPT; ++k) {
+        const int p = threadIdx.x + k * kThreads;
+        if (p < HW) {
+          const int y = p / W, x = p - y * W;
+          float a = 0.0f;
+          for (int j = 0; j < K; ++j) {
+            const int ro = reflect(y + j - r, H) * W;
+            const float wy = s_lut[j];
+            for (int i = 0; i < K; ++i)
+              a = a + (wy * s_lut[i]) * s_img[ro + reflect(x + i - r, W)];
+          }
+          acc[k] = a;
+        }
+      }
+      gather = true;
+    } else if (X && NPT * kThreads <= kMaxElasticHW && kind == SK_ELASTIC) {
+      // (only the instantiation for maps of up to 1024 pixels holds this stage)
+      const float* xr = ext + (size_t)rid * AVD_AUG_XREC;
+      const float alpha = xr[AVD_AUG_XELA_ALPHA], sigma = xr[AVD_AUG_XELA_SIGMA];
+      if (alpha == 0.0f || !(sigma > 0.0f) || HW > kMaxElasticHW) continue;
+      const int K = elastic_taps(sigma), r = K / 2;
+      if (r > H - 1 || r > W - 1) continue;
+      float* fx = s_img + HW;
+      float* fy = fx + HW;
+      float* tx = fy + HW;
+      float* ty = tx + HW;
+      gauss_taps(s_lut, K, sigma);
+      for (int p = threadIdx.x; p < HW; p += kThreads) {
+        fx[p] = elastic_noise(seed, (unsigned)rid, 0u, (unsigned)p);
+        fy[p] = elastic_noise(seed, (unsigned)rid, 1u, (unsigned)p);
+      }
+      __syncthreads();
+      for (int p = threadIdx.x; p < HW; p += kThreads) {      // rows
+        const int y = p / W, x = p - y * W;
+        float ax = 0.0f, ay = 0.0f;
+#pragma unroll 5      // the taps' LDS reads in flight together; the sum keeps its order
+        for (int j = 0; j < K; ++j) {
+          const int q = y * W + reflect(x + j - r, W);
+          ax = ax + s_lut[j] * fx[q];
+          ay = ay + s_lut[j] * fy[q];
+        }
+        tx[p] = ax;
+        ty[p] = ay;
+      }
+      __syncthreads();
+      for (int p = threadIdx.x; p < HW; p += kThreads) {      // columns
+        const int y = p / W, x = p - y * W;
+        float ax = 0.0f, ay = 0.0f;
+#pragma unroll 5      // the taps' LDS reads in flight together; the sum keeps its order
+        for (int j = 0; j < K; ++j) {
+          const int q = reflect(y + j - r, H) * W + x;
+          ax = ax + s_lut[j] * tx[q];
+          ay = ay + s_lut[j] * ty[q];
+        }
+        fx[p] = ax;
+        fy[p] = ay;
+      }
+      __syncthreads();
+      // torchvision scales dx by alpha / H and dy by alpha / W in normalised units; grid_sample
+      // (align_corners=False) turns a normalised d into d * W / 2 (x) or d * H / 2 (y) pixels
+      const float sx = (alpha * (float)W) / (2.0f * (float)H);
+      const float sy = (alpha * (float)H) / (2.0f * (float)W);
+#pragma unroll
+      for (int k = 0; k < NPT; ++k) {
+        const int p = threadIdx.x + k * kThreads;
+        if (p < HW) {
+          const int y = p / W, x = p - y * W;
+          // the displaced position as integer cell + fraction of the displacement alone: the
+          // fraction keeps the displacement's bits where x + d would round them away
+          const float dx = fx[p] * sx, dy = fy[p] * sy;
+          const float flx = fminf(fmaxf(floorf(dx), -65536.0f), 65536.0f);
+          const float fly = fminf(fmaxf(floorf(dy), -65536.0f), 65536.0f);
+          const int x0 = x + (int)flx, y0 = y + (int)fly;
+          const float lx = dx - flx, ly = dy - fly;
+          const float hx = 1.0f - lx, hy = 1.0f - ly;
+          const bool bx0 = x0 >= 0 && x0 < W, bx1 = x0 + 1 >= 0 && x0 + 1 < W;
+          const bool by0 = y0 >= 0 && y0 < H, by1 = y0 + 1 >= 0 && y0 + 1 < H;
+          const bool i00 = by0 && bx0, i01 = by0 && bx1, i10 = by1 && bx0, i11 = by1 && bx1;
+          const float v00 = i00 ? s_img[y0 * W + x0] : 0.0f;
+          const float v01 = i01 ? s_img[y0 * W + x0 + 1] : 0.0f;
+          const float v10 = i10 ? s_img[(y0 + 1) * W + x0] : 0.0f;
+          const float v11 = i11 ? s_img[(y0 + 1) * W + x0 + 1] : 0.0f;
+          const float m00 = i00 ? 1.0f : 0.0f, m01 = i01 ? 1.0f : 0.0f;
+          const float m10 = i10 ? 1.0f : 0.0f, m11 = i11 ? 1.0f : 0.0f;
+          const float sv = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+          const float mv = hy * (hx * m00 + lx * m01) + ly * (hx * m10 + lx * m11);
+          acc[k] = sv * mv;      // img * mask + (1 - mask) * fill, fill = 0
+        }
+      }
+      gather = true;
     } else {
       continue;
     }
@@ -410,7 +569,7 @@ __global__ __launch_bounds__(kThreads) void augment_seq_kernel(
 // of serial draws, not n blocks with one busy lane each; the grouped mask picks exactly k of the
 // ng groups with Floyd's algorithm (a uniformly random k-subset, like randperm(ng)[:k]) on a
 // per-thread bitmask in LDS.
-struct Chain { float st[kMaxStages * kStageF]; int n; };
+struct Chain { float st[kMaxStagesX * kStageF]; int n; };
 
 struct Urng {
   unsigned long long seed;
@@ -437,12 +596,15 @@ __device__ void inv_affine(float angle_deg, float tx, float ty, float s, float* 
 
 constexpr int kRecThreads = 64;
 
+// X (avd_augment_records_x): also the elastic and blur stages, into ext[n, AVD_AUG_XREC]
+template <bool X = false>
 __global__ __launch_bounds__(kRecThreads) void aug_records_kernel(Chain ch, int n, int H, int W,
                                                                   int group,
                                                                   unsigned long long seed,
                                                                   float* __restrict__ recs,
                                                                   uint32_t* __restrict__ gm,
-                                                                  int gm_words) {
+                                                                  int gm_words,
+                                                                  float* __restrict__ ext = nullptr) {
   // the grouped-mask bitmask of each thread: word-major [word][thread] (conflict-free when the
   // lanes touch the same word index)
   __shared__ uint32_t bits[kMaxGroups / 32][kRecThreads];
@@ -454,6 +616,7 @@ __global__ __launch_bounds__(kRecThreads) void aug_records_kernel(Chain ch, int 
   for (int i = 0; i < AVD_AUG_REC; ++i) r[i] = 0.f;
   r[AVD_AUG_GM] = -1.f;
   int flags = 0, gk = -1, gon = 0;
+  float xr[AVD_AUG_XREC] = {0.f, 0.f, 0.f, 0.f};
   const float area = (float)(H * W);
   for (int si = 0; si < ch.n; ++si) {
     const float* a = ch.st + si * kStageF;
@@ -519,10 +682,19 @@ __global__ __launch_bounds__(kRecThreads) void aug_records_kernel(Chain ch, int 
       gk = (int)(q[0] * (float)ng);
       gon = on;
       if (on) r[AVD_AUG_GM] = (float)rid;
+    } else if (X && kind == SK_ELASTIC) {
+      // ElasticTransform(alpha, sigma): fixed parameters, the fields are drawn by the view kernel
+      if (on) { xr[AVD_AUG_XELA_ALPHA] = q[0]; xr[AVD_AUG_XELA_SIGMA] = q[1]; }
+    } else if (X && kind == SK_BLUR) {
+      // GaussianBlur.get_params: one sigma ~ U(min, max) for both axes
+      const float sigma = rng.uni(q[1], q[2]);
+      if (on) { xr[AVD_AUG_XBLUR_SIGMA] = sigma; xr[AVD_AUG_XBLUR_K] = q[0]; }
     }
   }
   r[AVD_AUG_FLAGS] = (float)flags;
   for (int i = 0; i < AVD_AUG_REC; ++i) rec[i] = r[i];
+  if constexpr (X)
+    for (int i = 0; i < AVD_AUG_XREC; ++i) ext[(size_t)rid * AVD_AUG_XREC + i] = xr[i];
   if (gk < 0 || !gm) return;
   // exactly k distinct groups (Floyd): for j = ng-k .. ng-1 draw t uniform in [0, j]; take t,
   // or j when t is taken already -- every k-subset equally likely
@@ -672,8 +844,97 @@ extern "C" int avd_augment_records(const float* stages, int nstages, int n, int 
     const int ng = (H / group) * (W / group);
     if (ng > kMaxGroups || gm_words * 32 < ng) return AVD_ERR_SHAPE;
   }
-  aug_records_kernel<<<avd_cdiv(n, kRecThreads), kRecThreads, 0, avd_stream(stream)>>>(
+  aug_records_kernel<false><<<avd_cdiv(n, kRecThreads), kRecThreads, 0, avd_stream(stream)>>>(
       ch, n, H, W, group, seed, rec, has_gm ? gm : nullptr, gm_words);
+  AVD_CHECK_LAUNCH();
+  return AVD_OK;
+}
+
+// ------------------------------------------------------------------- elastic / blur (the _x exports)
+extern "C" int avd_augment_views_x(const uint8_t* src_u8, const int64_t* idx, long long n_src, int B,
+                                   int V, int H, int W, const float* lut, const float* rec,
+                                   const uint32_t* gm, int gm_words, int group,
+                                   unsigned long long seed, int order, const int* kinds, int nkinds,
+                                   void* out, int odt, const float* ext, void* stream) {
+  if (!src_u8 || !idx || !lut || !rec || !out || (nkinds > 0 && !kinds)) return AVD_ERR_ARG;
+  if (B <= 0 || V <= 0 || H <= 0 || W <= 0 || n_src <= 0) return AVD_ERR_SHAPE;
+  if ((long long)H * W > kMaxHW || (H * W) % 4 || W % 2 || order < 0 || order > 1) return AVD_ERR_SHAPE;
+  if (nkinds < 0 || nkinds > kMaxStagesX) return AVD_ERR_SHAPE;
+  Prog prog{};
+  prog.n = nkinds;
+  bool has_gm = false, has_ela = false, has_blur = false;
+  for (int i = 0; i < nkinds; ++i) {
+    if (kinds[i] < SK_CROP || kinds[i] > SK_BLUR) return AVD_ERR_ARG;
+    prog.kind[i] = kinds[i];
+    has_gm |= kinds[i] == SK_GMASK;
+    has_ela |= kinds[i] == SK_ELASTIC;
+    has_blur |= kinds[i] == SK_BLUR;
+  }
+  if ((has_ela || has_blur) && !ext) return AVD_ERR_ARG;
+  if (gm && has_gm && (group <= 0 || H % group || W % group ||
+                       gm_words * 32 < (H / group) * (W / group)))
+    return AVD_ERR_SHAPE;
+  // the elastic fields live in the image buffer's tail; a blur needs its reflect padding defined
+  // for the smallest kernel (per-record sizes: avd_augment_records_x, avdino.augment)
+  if (has_ela && H * W > kMaxElasticHW) return AVD_ERR_SHAPE;
+  if (has_blur && (kMinBlurK / 2 > H - 1 || kMinBlurK / 2 > W - 1)) return AVD_ERR_SHAPE;
+  if (odt != AVD_F32 && odt != AVD_BF16) return AVD_ERR_DTYPE;
+  const int npt = avd_cdiv(H * W, kThreads);
+  hipStream_t st = avd_stream(stream);
+#define AVD_SEQX_LAUNCH(TO, N)                                                                   \
+  augment_seq_kernel<TO, N, true><<<B * V, kThreads, 0, st>>>(src_u8, idx, V, B, H, W, lut, rec,  \
+                                                              gm, gm_words, group, seed, order,   \
+                                                              prog, (TO*)out, ext)
+  if (npt <= 4) {
+    if (odt == AVD_F32) AVD_SEQX_LAUNCH(float, 4); else AVD_SEQX_LAUNCH(bf16, 4);
+  } else if (npt <= 16) {
+    if (odt == AVD_F32) AVD_SEQX_LAUNCH(float, 16); else AVD_SEQX_LAUNCH(bf16, 16);
+  } else {
+    if (odt == AVD_F32) AVD_SEQX_LAUNCH(float, 49); else AVD_SEQX_LAUNCH(bf16, 49);
+  }
+#undef AVD_SEQX_LAUNCH
+  AVD_CHECK_LAUNCH();
+  return AVD_OK;
+}
+
+extern "C" int avd_augment_records_x(const float* stages, int nstages, int n, int H, int W,
+                                     int group, unsigned long long seed, float* rec, uint32_t* gm,
+                                     int gm_words, float* ext, void* stream) {
+  if (!stages || !rec) return AVD_ERR_ARG;
+  if (nstages < 0 || nstages > kMaxStagesX || n <= 0 || H <= 0 || W <= 0) return AVD_ERR_SHAPE;
+  Chain ch{};
+  ch.n = nstages;
+  bool has_gm = false, has_x = false;
+  for (int i = 0; i < nstages * kStageF; ++i) ch.st[i] = stages[i];
+  for (int i = 0; i < nstages; ++i) {
+    const float* a = stages + i * kStageF;
+    const int kind = (int)a[0];
+    if (kind < SK_CROP || kind > SK_BLUR) return AVD_ERR_ARG;
+    has_gm |= kind == SK_GMASK;
+    has_x |= kind >= SK_ELASTIC;
+    const int rmax = (H < W ? H : W) - 1;      // reflect padding is defined up to this radius
+    if (kind == SK_ELASTIC) {
+      if (!(a[3] > 0.0f) || H * W > kMaxElasticHW || elastic_taps(a[3]) / 2 > rmax)
+        return AVD_ERR_SHAPE;
+    } else if (kind == SK_BLUR) {
+      const int K = (int)a[2];
+      if ((float)K != a[2] || K < kMinBlurK || K > kMaxBlurK || !(K & 1) || K / 2 > rmax ||
+          !(a[3] > 0.0f) || a[4] < a[3])
+        return AVD_ERR_SHAPE;
+    }
+  }
+  if (has_x && !ext) return AVD_ERR_ARG;
+  if (has_gm) {
+    if (!gm || group <= 0 || H % group || W % group) return AVD_ERR_SHAPE;
+    const int ng = (H / group) * (W / group);
+    if (ng > kMaxGroups || gm_words * 32 < ng) return AVD_ERR_SHAPE;
+  }
+  if (ext)
+    aug_records_kernel<true><<<avd_cdiv(n, kRecThreads), kRecThreads, 0, avd_stream(stream)>>>(
+        ch, n, H, W, group, seed, rec, has_gm ? gm : nullptr, gm_words, ext);
+  else
+    aug_records_kernel<false><<<avd_cdiv(n, kRecThreads), kRecThreads, 0, avd_stream(stream)>>>(
+        ch, n, H, W, group, seed, rec, has_gm ? gm : nullptr, gm_words);
   AVD_CHECK_LAUNCH();
   return AVD_OK;
 }
