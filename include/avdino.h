@@ -331,6 +331,32 @@ int avd_softmax_rows_fwd(float* s, long long ld, int R, int C, void* stream);
 int avd_softmax_rows_bwd(const float* p, long long ldp, float* dp, long long lddp, int R, int C,
                          void* stream);
 
+/* The recurrence of a one-layer bidirectional nn.LSTM followed by the mean over time (lstm.hip;
+ * LSTMAudioEncoder.forward, models/dino.py:149-156), for N sequences of T steps, hidden size H
+ * (a multiple of 16, 16..128, else AVD_ERR_SHAPE).  Row (n, t, d) of a [N][T][2] grid is
+ * (n * T + t) * 2 + d, d = 0 the forward direction, 1 the reverse one (t = T-1 .. 0).
+ *   gx    [N][T][2][4H]  the input projections x W_ih^T + b_ih + b_hh (gate order i, f, g, o);
+ *   whh_f / whh_r [4H][H] weight_hh_l0 / weight_hh_l0_reverse;
+ *   out   [N][2H]        mean_t [h_fwd(t), h_rev(t)]; h0 = c0 = 0.
+ * dt = AVD_BF16: bf16 MFMA, W_hh and the fed-back h rounded to bf16, everything else f32;
+ * dt = AVD_F32: the f32 MFMA, an exact f32 fma chain.  All buffers are f32 in both.
+ * save_state != 0 also writes what avd_lstm_bwd reads, save [avd_lstm_ws save_elems]:
+ *   act   [N][T][2][5][H] sigmoid(i), sigmoid(f), tanh(g), sigmoid(o), c of every step, then
+ *   hprev [N][T][2][H]    the h that step consumed (zeros at a direction's first step), so that
+ *                         dW_hh = dG^T hprev is one strided GEMM over the N*T rows;
+ * with save_state == 0 (teacher, eval) save is not touched and may be NULL.
+ * avd_lstm_bwd: dout [N][2H] = the gradient of out (the mean's 1/T is applied here) ->
+ *   dg [N][T][2][4H] the pre-activation gate gradients (= the gradient of gx).
+ * One block owns 16 sequences of one direction for all T steps: no atomics, bitwise reproducible. */
+int avd_lstm_ws(int N, int T, int H, long long* save_elems, long long* dg_elems);
+int avd_lstm_fwd(const float* gx, const float* whh_f, const float* whh_r, float* out, float* save,
+                 int save_state, int dt, int N, int T, int H, void* stream);
+int avd_lstm_bwd(const float* dout, const float* whh_f, const float* whh_r, const float* save,
+                 float* dg, int dt, int N, int T, int H, void* stream);
+/* dst[i] = (dst type) src[i], i < n: AVD_BF16 -> AVD_F32 or AVD_F32 -> AVD_BF16 (round to nearest
+ * even), else AVD_ERR_DTYPE -- the NHWC bf16 token map into the f32 GEMMs and its gradient back. */
+int avd_cast(const void* src, int src_dt, void* dst, int dst_dt, long long n, void* stream);
+
 /* Test hook: fill the LDS of every CU with NaN bit patterns (0x7fc07fc0), so a kernel that reads
  * LDS it never wrote sees NaN instead of a benign leftover (tools/lds_poison.py). */
 int avd_lds_poison(void* stream);

@@ -82,6 +82,10 @@ PROTOS = {
     "avd_gate_bwd": [P, L, P, L, P, P, P, L, P, P, P, L, I, I, P],
     "avd_softmax_rows_fwd": [P, L, I, I, P],
     "avd_softmax_rows_bwd": [P, L, P, L, I, I, P],
+    "avd_lstm_ws": [I, I, I, P, P],
+    "avd_lstm_fwd": [P, P, P, P, P, I, I, I, I, I, P],
+    "avd_lstm_bwd": [P, P, P, P, P, I, I, I, I, P],
+    "avd_cast": [P, I, P, I, L, P],
     "avd_cl_layer_bwd_slabs": [I, I, I, I, I, I, I, I],
     "avd_cl_layer_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     "avd_cl_layer_bwd_codes": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],

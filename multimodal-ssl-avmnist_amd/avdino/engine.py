@@ -24,8 +24,8 @@ import torch
 
 from . import contrastive, ops
 from .capture import GraphedStep, host_point, new_event  # noqa: F401  (GraphedStep re-exported)
-from .spec import (HEAD_NAMES, MIX_KIND, MULTI_ENCODERS, PROJ_HIDDEN, UNI_ALIASES, UNI_ENCODERS,
-                   XATTN_NAMES)
+from .spec import (HEAD_NAMES, LSTM_PROJ, MIX_KIND, MULTI_ENCODERS, PROJ_HIDDEN, UNI_ALIASES,
+                   UNI_ENCODERS, XATTN_NAMES, lstm_hidden)
 
 F32 = torch.float32
 # early gradient buckets at a host point inside the step (False: one all-reduce after the step)
@@ -107,11 +107,15 @@ class ConvBranch:
     flatten order, or -- ``hwc`` (bf16, flatten tails) -- the last pooled map itself, bf16 NHWC,
     for the encoder Linear's (h, w, c)-ordered kernels (avd_linear_*_hwc)."""
 
-    def __init__(self, stack, act_dtype, fp8=False, hwc=False):
+    def __init__(self, stack, act_dtype, fp8=False, hwc=False, nhwc_tail=False):
         self.stack = stack
         self.act = act_dtype
         self.dims = stack.layer_dims()
         self.hwc = bool(hwc) and act_dtype == torch.bfloat16 and not stack.gap
+        # nhwc_tail: the last pooled map itself, NHWC, in EITHER activation dtype (the LSTM
+        # encoder's token rows); only that encoder sets it, so no other stack changes route
+        if nhwc_tail and not stack.gap:
+            self.hwc = True
         # fp8: the layers after the first run their forward, input gradient AND weight gradient
         # on the block-scaled e4m3 MFMA (config 5's "fp8 MFMA conv path", avd_mx_conv_*: both
         # operands quantised to e4m3 while staged, one E8M0 scale per strip / 32-k block); the
@@ -1672,22 +1676,121 @@ class MultiCentralEngine:
 
 
 # ============================================================================ unimodal DINO
+def lstm_forward(ws, tag, x, N, T, H, prm, gm, bf16, train):
+    """One-layer bidirectional nn.LSTM + mean over time on token rows x [N*T, I] (f32):
+    Gx = x W_ih^T + (b_ih + b_hh) per direction as GEMMs into [N, T, 2, 4H], then the recurrence
+    (avd_lstm_fwd).  prm(name) -> the tensor of an nn.LSTM parameter name (weight_ih_l0, ...,
+    bias_hh_l0_reverse).  Returns (out [N, 2H], saved state or None when not train)."""
+    R = N * T
+    ns, ng = ops.lstm_ws(N, T, H)
+    gx = ws.get(f"{tag}.gx", ng)
+    bsum = ws.get(f"{tag}.bsum", 8 * H)
+    for d, sfx in enumerate(("", "_reverse")):
+        b = bsum[d * 4 * H:(d + 1) * 4 * H]
+        b.copy_(prm("bias_ih_l0" + sfx))
+        ops.axpy(b, prm("bias_hh_l0" + sfx))
+        ops.linear_fwd(x, prm("weight_ih_l0" + sfx), b, gx, R, out_ld=8 * H, out_off=d * 4 * H, mode=gm)
+    save = ws.get(f"{tag}.save", ns) if train else None
+    out = ws.get(f"{tag}.lstm", N * 2 * H)
+    ops.lstm_fwd(gx, prm("weight_hh_l0"), prm("weight_hh_l0_reverse"), out, save, N, T, H, bf16)
+    return out.view(N, 2 * H), save
+
+
+def lstm_backward(ws, x, save, dout, N, T, H, prm, grad, gm, bf16):
+    """Backward of lstm_forward: dout [N, 2H] -> the eight parameter gradients (grad(name) -> the
+    tensor to write) and, returned, the gradient of x [N*T, I].  The recurrence (avd_lstm_bwd)
+    gives dG; every weight gradient is a GEMM over the N*T rows."""
+    R = N * T
+    I = prm("weight_ih_l0").shape[1]
+    _ns, ng = ops.lstm_ws(N, T, H)
+    dg = ws.get("lstm.dg", ng)
+    ops.lstm_bwd(dout, prm("weight_hh_l0"), prm("weight_hh_l0_reverse"), save, dg, N, T, H, bf16)
+    hprev = save[ops.lstm_hprev_offset(N, T, H):]
+    dx = ws.get("lstm.dx", R * I)
+    for d, sfx in enumerate(("", "_reverse")):
+        wih, whh = prm("weight_ih_l0" + sfx), prm("weight_hh_l0" + sfx)
+        off = d * 4 * H
+        # dW_ih = dG^T x and both bias gradients (the same column sums of dG)
+        dbi = grad("bias_ih_l0" + sfx)
+        ops.linear_bwd(dg, x, wih, grad("weight_ih_l0" + sfx), dbi, None, R, dout_ld=8 * H,
+                       dout_off=off, mode=gm)
+        grad("bias_hh_l0" + sfx).copy_(dbi)
+        # dW_hh = dG^T hprev: one strided GEMM over the N*T rows
+        ops.linear_bwd(dg, hprev, whh, grad("weight_hh_l0" + sfx), None, None, R, dout_ld=8 * H,
+                       dout_off=off, x_ld=2 * H, x_off=d * H, mode=gm)
+        # dx = sum over the directions of dG W_ih
+        ops.gemm(R, I, 4 * H, dg, 8 * H, 1, wih, I, 1, dx, I, beta=float(d), a_off=off, mode=gm)
+    return dx
+
+
 class UniEncoder:
     """An UNIMODAL_MODEL_MAP encoder (run_dino.py:542-550) on channels-last maps: conv stack
     (ConvBranch) then its Linear chain -- ImageEncoder: GAP -> Linear(128,512) -> Linear(512,D)
     (dino.py:483-499); SpectrogramEncoder: GAP -> Linear(256,D) (502-513);
-    SpectrogramEncoderCentral: CentralUnimodalAudio flatten -> Linear(3136,D) (515-523)."""
+    SpectrogramEncoderCentral: CentralUnimodalAudio flatten -> Linear(3136,D) (515-523);
+    SpectrogramEncoderLSTM (525-530, LSTMAudioEncoder 117-156; ``out_dim`` required): the pooled
+    14 x 14 x 128 map as 196 token rows -> Linear(128,64) + ReLU per token -> bidirectional
+    LSTM(64, D/2) -> mean over the tokens.  The input projections and every weight gradient are
+    GEMMs; the recurrence is avd_lstm_fwd / avd_lstm_bwd."""
 
-    def __init__(self, kind, prefix, act_dtype, gemm_mode):
-        modality, stack, lins, _sd = UNI_ENCODERS[UNI_ALIASES.get(kind, kind)]
+    def __init__(self, kind, prefix, act_dtype, gemm_mode, out_dim=None):
+        kind = UNI_ALIASES.get(kind, kind)
+        modality, stack, lins, _sd = UNI_ENCODERS[kind]
         self.modality = modality
         self.hw = 28 if modality == "image" else 112
-        self.branch = ConvBranch(stack(prefix), act_dtype)
+        self.lstm = kind == "spectrogram_lstm"
+        self.branch = ConvBranch(stack(prefix), act_dtype, nhwc_tail=self.lstm)
         self.lins = [f"{prefix}.{k}" for k in lins]
         self.gm = gemm_mode
+        if self.lstm:
+            self.H = lstm_hidden(out_dim)
+            self.lk = f"{prefix}.encoder.lstm."
+            self.bf16 = act_dtype == torch.bfloat16
+
+    # ---- the LSTM tail
+    def _lstm_forward(self, ws, store, tag, feat, N, train):
+        """feat: the NHWC pooled map [N, T, C] (act dtype) -> (mean_t h [N, 2H], saved)."""
+        C, T = self.branch.feat_shape()
+        R, Pj = N * T, LSTM_PROJ
+        if feat.dtype == F32:
+            tok = feat.reshape(-1)
+        else:                               # the GEMMs read f32 storage
+            tok = ws.get(f"{tag}.tok", R * C)
+            ops.cast(feat.reshape(-1), tok, R * C)
+        k = self.lins[0]
+        pre = ws.get(f"{tag}.pre", R * Pj)
+        ops.linear_fwd(tok, store[k + ".weight"], store[k + ".bias"], pre, R, mode=self.gm)
+        xp = ws.get(f"{tag}.xp", R * Pj)
+        ops.act_fwd(pre, xp, 0, None, None, R, 1, Pj, 0.0, 0)
+        out, save = lstm_forward(ws, tag, xp, N, T, self.H, lambda n: store[self.lk + n], self.gm,
+                                 self.bf16, train)
+        return out, (tok, pre, xp, save)
+
+    def _lstm_backward(self, ws, store, saved, dout, N):
+        """dout [N, 2H] -> parameter gradients of the LSTM and feature_proj; returns the token
+        gradient as the map gradient (NHWC, act dtype)."""
+        tok, pre, xp, save = saved
+        C, T = self.branch.feat_shape()
+        R, Pj = N * T, LSTM_PROJ
+        dxp = lstm_backward(ws, xp, save, dout, N, T, self.H, lambda n: store[self.lk + n],
+                            lambda n: store.grad_of(self.lk + n), self.gm, self.bf16)
+        dpre = ws.get("uni.dpre", R * Pj)
+        ops.act_bwd(pre, dxp, dpre, 0, None, None, R, 1, Pj, 0.0, 0)
+        k = self.lins[0]
+        dtok = ws.get("uni.dtok", R * C)
+        ops.linear_bwd(dpre, tok, store[k + ".weight"], store.grad_of(k + ".weight"),
+                       store.grad_of(k + ".bias"), dtok, R, mode=self.gm)
+        if self.branch.act == F32:
+            return dtok
+        dmap = ws.get("uni.dmap", R * C, self.branch.act)
+        ops.cast(dtok, dmap, R * C)
+        return dmap
 
     def forward(self, ws, store, tag, x, N, G, need_dgrad):
         feat, ctx = self.branch.forward(ws, store, tag, x, N, G, True, need_dgrad)
+        if self.lstm:
+            out, saved = self._lstm_forward(ws, store, tag, feat, N, need_dgrad)
+            return out, (ctx, saved)
         acts = [feat]
         h = feat
         for i, k in enumerate(self.lins):
@@ -1700,6 +1803,8 @@ class UniEncoder:
 
     def forward_eval(self, ws, store, tag, x, N):
         h = self.branch.forward_eval(ws, store, tag, x, N)
+        if self.lstm:
+            return self._lstm_forward(ws, store, tag, h, N, False)[0]
         for i, k in enumerate(self.lins):
             w = store[k + ".weight"]
             out = ws.get(f"{tag}.lin{i}", N * w.shape[0])
@@ -1710,6 +1815,9 @@ class UniEncoder:
     def backward(self, ws, store, ctx, dout):
         bctx, acts = ctx
         N = bctx["N"]
+        if self.lstm:
+            self.branch.backward(ws, store, bctx, self._lstm_backward(ws, store, acts, dout, N))
+            return
         g = dout
         for i in reversed(range(len(self.lins))):
             k = self.lins[i]
@@ -1748,8 +1856,8 @@ class UniModalEngine:
         self.gm = ops.GEMM_BF16_MFMA if act_dtype == torch.bfloat16 else ops.GEMM_F32_MFMA
         self.cos_alpha = float(cos_alpha)
         self.ws = Workspace(store.device)
-        self.enc = UniEncoder(self.kind, "student", act_dtype, self.gm)
-        self.t_enc = UniEncoder(self.kind, "teacher", act_dtype, self.gm)
+        self.enc = UniEncoder(self.kind, "student", act_dtype, self.gm, out_dim=D)
+        self.t_enc = UniEncoder(self.kind, "teacher", act_dtype, self.gm, out_dim=D)
         self.modality = self.enc.modality
         self.sproj = ProjHead("student_projection", D, P, gemm_mode=self.gm)
         self.tproj = ProjHead("teacher_projection", D, P, gemm_mode=self.gm)

@@ -42,7 +42,7 @@ import torch.nn as nn
 from . import contrastive, ops
 from .engine import Hyper, MultiCentralEngine, SimCLREngine, UniModalEngine, Workspace, ema_step
 from .params import ParamStore
-from .spec import MULTI_ENCODERS, multimodal_dino_sd, simclr_sd, unimodal_dino_sd
+from .spec import LSTM_DIMS, MULTI_ENCODERS, multimodal_dino_sd, simclr_sd, unimodal_dino_sd
 
 try:  # a real drop-in under Lightning's Trainer where Lightning is installed
     from lightning.pytorch import LightningModule as _LightningBase
@@ -162,11 +162,27 @@ class SpectrogramEncoderCentral(SpectrogramEncoder):
     kind = "spectrogram_central"
 
 
+class SpectrogramEncoderLSTM(SpectrogramEncoder):
+    """LSTMAudioEncoder (models/dino.py:117-156, 525-530): the first three blocks of the 3x3 audio
+    CNN (1->32->64->128), Linear(128, 64) + ReLU per pooled position, one bidirectional
+    nn.LSTM(64, output_dim // 2) over the 14 x 14 = 196 positions, mean over them.  Descriptor:
+    the recurrence is avd_lstm_fwd / avd_lstm_bwd (csrc/lstm.hip)."""
+    kind = "spectrogram_lstm"
+    SUPPORTED_DIMS = LSTM_DIMS
+
+    def __init__(self, output_dim=256):
+        if output_dim not in self.SUPPORTED_DIMS:
+            raise ValueError(f"SpectrogramEncoderLSTM: output_dim must be one of {self.SUPPORTED_DIMS} "
+                             f"(twice a hidden size the recurrence kernel serves), got {output_dim}")
+        super().__init__(output_dim)
+
+
 MODEL_MAP = {"multi_simple": SimpleMultiModalEncoder, "multi_simple_gated": GatedMultiModalEncoder,
              "multi_cross_attention": CrossAttentionMultiModalEncoder,
              "multi_central": CentralMultiModalEncoder}
 UNIMODAL_MODEL_MAP = {"image_simple": ImageEncoder, "spectrogram_simple": SpectrogramEncoder,
-                      "spectrogram_central": SpectrogramEncoderCentral}
+                      "spectrogram_central": SpectrogramEncoderCentral,
+                      "spectrogram_lstm": SpectrogramEncoderLSTM}
 
 
 def _device(device):
@@ -946,8 +962,8 @@ class UniModalDINO(_ArenaModule):
         enc = encoder_class(**encoder_kwargs)
         if getattr(enc, "kind", None) is None:
             raise NotImplementedError(
-                f"{encoder_class.__name__}: the MI355X engine runs ImageEncoder, SpectrogramEncoder "
-                f"and SpectrogramEncoderCentral")
+                f"{encoder_class.__name__}: the MI355X engine runs ImageEncoder, SpectrogramEncoder, "
+                f"SpectrogramEncoderCentral and SpectrogramEncoderLSTM")
         self.student_spec = enc
         self.projection_dim, self.output_dim = projection_dim, output_dim
         self.momentum, self.center_momentum, self.dropout = momentum, center_momentum, dropout

@@ -1162,6 +1162,73 @@ def softmax_rows_bwd(pr, dp, R, C, ldp=None, lddp=None):
     call("avd_softmax_rows_bwd", p(pr), ldp, p(dp), lddp, R, C, stream())
 
 
+# ---------------------------------------------------------------- LSTM recurrence (lstm.hip)
+LSTM_HIDDEN = tuple(range(16, 129, 16))   # hidden sizes the recurrence kernel serves
+LSTM_BLOCK = 16                           # sequences per workgroup
+
+
+def _lstm_dims(N, T, H):
+    _need(H in LSTM_HIDDEN, f"lstm: hidden size must be one of {LSTM_HIDDEN} (got {H})")
+    _need(N >= 1 and T >= 1, "lstm: N, T >= 1")
+
+
+def _lstm_f32(t, n, what):
+    _need(t is not None and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n,
+          f"lstm {what}: contiguous f32 with >= {n} elements")
+
+
+def lstm_ws(N, T, H):
+    """(saved-state elements, dG elements) of avd_lstm_fwd(save) / avd_lstm_bwd, f32 each."""
+    _lstm_dims(N, T, H)
+    a, b = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    call("avd_lstm_ws", N, T, H, ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
+
+
+def lstm_hprev_offset(N, T, H):
+    """Element offset, inside the saved state, of hprev [N][T][2][H]: the h each step consumed."""
+    _lstm_dims(N, T, H)
+    return N * T * 2 * 5 * H
+
+
+def lstm_fwd(gx, whh_f, whh_r, out, save, N, T, H, bf16):
+    """out [N, 2H] = mean over t of the bidirectional LSTM's h from the input projections
+    gx [N, T, 2, 4H] (avd_lstm_fwd); save: the backward's state buffer, or None (not touched)."""
+    _lstm_dims(N, T, H)
+    ns, ng = lstm_ws(N, T, H)
+    _lstm_f32(gx, ng, "gx")
+    _lstm_f32(whh_f, 4 * H * H, "weight_hh")
+    _lstm_f32(whh_r, 4 * H * H, "weight_hh (reverse)")
+    _lstm_f32(out, N * 2 * H, "out")
+    if save is not None:
+        _lstm_f32(save, ns, "saved state")
+    _timed(f"lstm_fwd[{N}x{T}x{H} bf{int(bool(bf16))}]", 4 * (ng + (ns if save is not None else 0)),
+           2 * N * T * 2 * 4 * H * H,
+           lambda: call("avd_lstm_fwd", p(gx), p(whh_f), p(whh_r), p(out), p(save),
+                        int(save is not None), BF16 if bf16 else F32, N, T, H, stream()))
+
+
+def lstm_bwd(dout, whh_f, whh_r, save, dg, N, T, H, bf16):
+    """dg [N, T, 2, 4H] = gradient of gx from dout [N, 2H] (avd_lstm_bwd; the mean's 1/T inside)."""
+    _lstm_dims(N, T, H)
+    ns, ng = lstm_ws(N, T, H)
+    _lstm_f32(dout, N * 2 * H, "dout")
+    _lstm_f32(whh_f, 4 * H * H, "weight_hh")
+    _lstm_f32(whh_r, 4 * H * H, "weight_hh (reverse)")
+    _lstm_f32(save, ns, "saved state")
+    _lstm_f32(dg, ng, "dg")
+    _timed(f"lstm_bwd[{N}x{T}x{H} bf{int(bool(bf16))}]", 4 * (ng + ns), 2 * N * T * 2 * 4 * H * H,
+           lambda: call("avd_lstm_bwd", p(dout), p(whh_f), p(whh_r), p(save), p(dg),
+                        BF16 if bf16 else F32, N, T, H, stream()))
+
+
+def cast(src, dst, n):
+    """dst[:n] = src[:n] between bf16 and f32 (avd_cast)."""
+    _need(n >= 1 and src.numel() >= n and dst.numel() >= n, "cast bounds")
+    _need({src.dtype, dst.dtype} == {torch.float32, torch.bfloat16}, "cast: bf16 <-> f32")
+    call("avd_cast", p(src), dtcode(src), p(dst), dtcode(dst), n, stream())
+
+
 def cosine_consistency(emb, V, B, D, alpha, loss_parts, demb):
     _need(emb.numel() >= V * B * D and (demb is None or demb.numel() >= V * B * D)
           and (loss_parts is None or loss_parts.numel() >= B), "cosine consistency shapes")

@@ -31,7 +31,7 @@ ALIGN = 16  # floats (64 B) per parameter slot
 
 
 def _is_param(kind):
-    return kind in ("w", "b", "bn_w", "bn_b", "gate")
+    return kind in ("w", "b", "bn_w", "bn_b", "gate", "lstm")
 
 
 def _dead(key):
@@ -164,8 +164,8 @@ class ParamStore:
     # ------------------------------------------------------------------ init / io
     def reset_parameters(self, seed=0):
         """PyTorch's default init for the reference layers (Conv2d/Linear kaiming-uniform(a=sqrt 5)
-        => U(+-1/sqrt(fan_in)) for weight and bias; BN weight 1, bias 0; the fusion
-        gates 0.5); the teacher starts as an exact copy of the student (dino.py:615-629)."""
+        => U(+-1/sqrt(fan_in)) for weight and bias; nn.LSTM U(+-1/sqrt(hidden)); BN weight 1,
+        bias 0; the fusion gates 0.5); the teacher starts as an exact copy of the student (dino.py:615-629)."""
         g = torch.Generator().manual_seed(seed)
         fan = {}
         for k, (shape, kind) in self.spec.items():
@@ -175,6 +175,11 @@ class ParamStore:
             shape, kind = self.spec[k]
             if kind in ("w", "b"):
                 b = 1.0 / math.sqrt(fan[k.rsplit(".", 1)[0]])
+                v = (torch.rand(shape, generator=g, dtype=torch.float64) * 2 - 1) * b
+            elif kind == "lstm":
+                # nn.LSTM.reset_parameters: every tensor, biases included, U(+-1/sqrt(hidden));
+                # hidden = a fourth of the leading (4H) dimension
+                b = 1.0 / math.sqrt(shape[0] // 4)
                 v = (torch.rand(shape, generator=g, dtype=torch.float64) * 2 - 1) * b
             elif kind == "bn_w":
                 v = torch.ones(shape, dtype=torch.float64)

@@ -85,8 +85,8 @@ class _UniEncoder:
     """One UNI_ENCODERS network under the state-dict prefix ``prefix``: a DINO model's
     ``student``, or a SimCLR tower (``image_encoder`` / ``audio_encoder``, spec.simclr_sd)."""
 
-    def __init__(self, kind, act, gm, prefix="student"):
-        self.enc = UniEncoder(kind, prefix, act, gm)
+    def __init__(self, kind, act, gm, prefix="student", out_dim=None):
+        self.enc = UniEncoder(kind, prefix, act, gm, out_dim=out_dim)
 
     def __call__(self, ws, st, x, N, train):
         if train:
@@ -184,7 +184,7 @@ class LinearProbe:
         elif self.multimodal:
             self.enc = _MultiEncoder(self.kind, E, D, act_dtype, self.gm, fusion_dropout)
         else:
-            self.enc = _UniEncoder(self.kind, act_dtype, self.gm, prefix)
+            self.enc = _UniEncoder(self.kind, act_dtype, self.gm, prefix, out_dim=D)
             self.modality = UNI_ENCODERS[self.kind][0]
         self.cls = ParamStore(classifier_sd(D), dev, seed=seed, has_teacher=False)
         if classifier_state is not None:

@@ -190,12 +190,16 @@ def model_stats(model, G, L, B=1):
     their projection heads and, for the modes with heads, the originals through the student
     branches and both heads; the cross-attention encoder's attention products grow with the batch
     size B of a call; parameters = every parameter tensor of the state dict (student,
-    teacher, heads, incl. the CentralNet fc1/fc2 the reference builds but never runs)."""
-    from .spec import MIX_KIND, MULTI_ENCODERS, UNI_ENCODERS, XATTN_NAMES
+    teacher, heads, incl. the CentralNet fc1/fc2 the reference builds but never runs).
+    spectrogram_lstm: after the conv stack, per sample and with T = 14 * 14 = 196 positions,
+    H = output_dim / 2:  T * 128 * 64  (feature_proj per position)
+                       + T * 2 * 4H * (64 + H)  (both directions: the input projection and the
+                                                 recurrent product of the four gates)."""
+    from .spec import LSTM_PROJ, MIX_KIND, MULTI_ENCODERS, UNI_ENCODERS, XATTN_NAMES
     m = model.model
     spec = m.store.spec
     params = sum(int(math.prod(shp)) for k, (shp, kind) in spec.items()
-                 if kind in ("w", "b", "bn_w", "bn_b", "gate"))
+                 if kind in ("w", "b", "bn_w", "bn_b", "gate", "lstm"))
 
     def lin(key):
         shp = spec[key + ".weight"][0]
@@ -224,7 +228,12 @@ def model_stats(model, G, L, B=1):
     else:
         kind = m.student_spec.kind
         _mod, stack, lins, _sd = UNI_ENCODERS[kind]
-        enc = _stack_macs(stack("student")) + sum(lin(f"student.{k}") for k in lins)
+        st = stack("student")
+        if kind == "spectrogram_lstm":
+            T, H = st.layer_dims()[-1][2] ** 2, m.output_dim // 2
+            enc = _stack_macs(st) + T * lin(f"student.{lins[0]}") + T * 2 * 4 * H * (LSTM_PROJ + H)
+        else:
+            enc = _stack_macs(st) + sum(lin(f"student.{k}") for k in lins)
         macs = (G + L) * (enc + head("student_projection")) + G * (enc + head("teacher_projection"))
     return macs / 1e9, params
 

@@ -207,9 +207,45 @@ def spectrogram_central_sd(sd, prefix, out_dim):
     _dense(sd, f"{prefix}.encoder.1", out_dim, 64 * 7 * 7)
 
 
+# SpectrogramEncoderLSTM (dino.py:525-530 over LSTMAudioEncoder, 117-156): the first three blocks
+# of the 3x3 audio CNN, Linear(128, LSTM_PROJ) + ReLU per pooled position, one bidirectional
+# nn.LSTM(LSTM_PROJ, output_dim // 2) over the 14 x 14 positions, mean over them.
+LSTM_PROJ = 64
+LSTM_HIDDEN = tuple(range(16, 129, 16))          # hidden sizes the recurrence kernel serves
+LSTM_DIMS = tuple(2 * h for h in LSTM_HIDDEN)    # = the supported output_dim values
+LSTM_KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+
+
+def lstm_hidden(out_dim):
+    """Hidden size per direction for an output_dim, or ValueError naming the supported ones."""
+    if out_dim not in LSTM_DIMS:
+        raise ValueError(f"spectrogram_lstm: output_dim must be one of {LSTM_DIMS} (an even "
+                         f"number whose half is a multiple of 16 up to 128), got {out_dim}")
+    return out_dim // 2
+
+
+def lstm_stack(prefix):
+    convs = CNN3_AUDIO_CONVS[:3]
+    n = len(convs)
+    return ConvStackSpec(convs, 112, False, [f"{prefix}.{4 * i}" for i in range(n)],
+                         [f"{prefix}.{4 * i + 1}" for i in range(n)])
+
+
+def spectrogram_lstm_sd(sd, prefix, out_dim):
+    H = lstm_hidden(out_dim)
+    for i, (ci, co, k, _p) in enumerate(CNN3_AUDIO_CONVS[:3]):
+        _dense(sd, f"{prefix}.encoder.cnn.{4 * i}", co, ci, k)
+        _bn(sd, f"{prefix}.encoder.cnn.{4 * i + 1}", co)
+    _dense(sd, f"{prefix}.encoder.feature_proj.0", LSTM_PROJ, 128)
+    for suffix in ("", "_reverse"):
+        for key, shape in zip(LSTM_KEYS, ((4 * H, LSTM_PROJ), (4 * H, H), (4 * H,), (4 * H,))):
+            sd[f"{prefix}.encoder.lstm.{key}{suffix}"] = (shape, "lstm")
+
+
 # UNIMODAL_MODEL_MAP encoders that run on the engine (run_dino.py:542-550):
 #   kind -> (modality, stack builder(prefix), [Linear keys after the stack, relative to prefix],
 #            state-dict builder)
+# (spectrogram_lstm: the one Linear is feature_proj, per token; the LSTM follows it)
 UNI_ENCODERS = {
     "image_simple": ("image", lambda p: cnn3_stack(f"{p}.encoder", CNN3_IMAGE_CONVS, 28),
                      ["encoder.14", "projection.0"], image_encoder_sd),
@@ -217,6 +253,8 @@ UNI_ENCODERS = {
                            ["encoder.18"], spectrogram_encoder_sd),
     "spectrogram_central": ("audio", lambda p: central_stack(f"{p}.encoder.0", CENTRAL_AUDIO_CONVS, 112),
                             ["encoder.1"], spectrogram_central_sd),
+    "spectrogram_lstm": ("audio", lambda p: lstm_stack(f"{p}.encoder.cnn"),
+                         ["encoder.feature_proj.0"], spectrogram_lstm_sd),
 }
 UNI_ALIASES = {"image": "image_simple", "audio": "spectrogram_simple"}
 

@@ -6,8 +6,8 @@ hardware.num_gpus) instead of a SLURM ``sbatch run_gpu.sbatch`` line.
     python -m avdino.submit_models --models multi_central image_simple --training_mode mse \\
         --config configs/config_multimodal_dino.yaml [--dry-run] [--log-dir DIR] [-- extra run_dino args]
 
-Models of the reference's list that are not on the MI355X hot path (the ViT / LSTM / ResNet /
-MobileViT encoders) are rejected with the list of supported ones.  Jobs run one
+Models of the reference's list that are not on the MI355X hot path (multi_lstm and the ViT /
+ResNet / MobileViT encoders) are rejected with the list of supported ones.  Jobs run one
 after another (the node's GPUs are shared by the ranks of one job); stdout / stderr go to
 ``{log_dir}/{model}{_mode}_{metric}_{timestamp}.out/.err`` as the reference names them.
 """
@@ -24,7 +24,7 @@ ALL_MODELS = ["multi_simple", "multi_simple_gated", "multi_lstm", "multi_vit", "
               "image_simple", "spectrogram_simple", "spectrogram_central", "spectrogram_lstm",
               "spectrogram_resnet", "spectrogram_vit", "spectrogram_mobile_vit"]
 MULTIMODAL = {"multi_central", "multi_simple", "multi_simple_gated", "multi_cross_attention"}
-UNIMODAL = {"image_simple", "spectrogram_simple", "spectrogram_central"}
+UNIMODAL = {"image_simple", "spectrogram_simple", "spectrogram_central", "spectrogram_lstm"}
 
 
 def parse_args(argv=None):
