@@ -108,6 +108,12 @@ class ConvBranch:
     for the encoder Linear's (h, w, c)-ordered kernels (avd_linear_*_hwc)."""
 
     def __init__(self, stack, act_dtype, fp8=False, hwc=False, nhwc_tail=False):
+        # every pass around the conv walks 2 x 2 pool windows: a stack with an unpooled layer
+        # (spec.lstm_image_stack) has no kernels here yet, and nothing stands in for them
+        if not all(stack.pools):
+            raise NotImplementedError(
+                "ConvBranch has no kernels for a conv block without a max-pool "
+                f"(pools = {stack.pools}): conv -> BN -> ReLU -> maxpool2 only")
         self.stack = stack
         self.act = act_dtype
         self.dims = stack.layer_dims()

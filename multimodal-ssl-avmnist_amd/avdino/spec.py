@@ -18,22 +18,34 @@ from collections import OrderedDict
 
 
 class ConvStackSpec:
-    """[conv(K, pad) -> BN2d -> ReLU -> maxpool2] x L (+ AdaptiveAvgPool2d(1) if gap)."""
+    """[conv(K, pad) -> BN2d -> ReLU -> maxpool2] x L (+ AdaptiveAvgPool2d(1) if gap).
+    ``pools``: per-layer pool flags (default: every layer pooled).  Only the last layer may go
+    without its pool, and only in front of an NHWC tail (``nhwc_tail``: the LSTM towers' token
+    rows) -- LSTMImageEncoder.cnn's last block (dino.py:75-115)."""
 
-    def __init__(self, convs, hw, gap, conv_keys, bn_keys):
+    def __init__(self, convs, hw, gap, conv_keys, bn_keys, pools=None, nhwc_tail=False):
         self.convs = convs            # [(cin, cout, k, pad)]
         self.hw = hw
         self.gap = gap
         self.conv_keys = conv_keys
         self.bn_keys = bn_keys
+        self.pools = tuple(bool(p) for p in pools) if pools is not None else (True,) * len(convs)
+        self.nhwc_tail = bool(nhwc_tail)
+        if len(self.pools) != len(convs):
+            raise ValueError(f"pools has {len(self.pools)} flags for {len(convs)} conv layers")
+        if not all(self.pools[:-1]):
+            raise ValueError("only the last conv layer may be unpooled")
+        if not self.pools[-1] and (gap or not self.nhwc_tail):
+            raise ValueError("an unpooled last layer needs nhwc_tail=True (and no gap)")
 
     def layer_dims(self):
-        """[(H_in, Ho, Hpool)] per layer (square maps)."""
+        """[(H_in, Ho, Hpool)] per layer (square maps); Hpool = Ho for an unpooled layer."""
         out, h = [], self.hw
-        for (_ci, _co, k, pad) in self.convs:
+        for (_ci, _co, k, pad), pool in zip(self.convs, self.pools):
             ho = h + 2 * pad - k + 1
-            out.append((h, ho, ho // 2))
-            h = ho // 2
+            hp = ho // 2 if pool else ho
+            out.append((h, ho, hp))
+            h = hp
         return out
 
     @property
@@ -229,6 +241,17 @@ def lstm_stack(prefix):
     n = len(convs)
     return ConvStackSpec(convs, 112, False, [f"{prefix}.{4 * i}" for i in range(n)],
                          [f"{prefix}.{4 * i + 1}" for i in range(n)])
+
+
+def lstm_image_stack(prefix):
+    """LSTMImageEncoder.cnn (dino.py:75-115): the 3x3 image CNN whose third block has no
+    MaxPool2d -- 28 -> 14 -> 7 -> 7, i.e. 49 tokens of 128 channels.  Sequential indices: the
+    missing pool shifts nothing before it, so the keys are cnn.0/1, 4/5, 8/9."""
+    convs = CNN3_IMAGE_CONVS
+    n = len(convs)
+    return ConvStackSpec(convs, 28, False, [f"{prefix}.{4 * i}" for i in range(n)],
+                         [f"{prefix}.{4 * i + 1}" for i in range(n)],
+                         pools=(True, True, False), nhwc_tail=True)
 
 
 def spectrogram_lstm_sd(sd, prefix, out_dim):
