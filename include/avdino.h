@@ -361,15 +361,19 @@ int avd_cast(const void* src, int src_dt, void* dst, int dst_dt, long long n, vo
  * LDS it never wrote sees NaN instead of a benign leftover (tools/lds_poison.py). */
 int avd_lds_poison(void* stream);
 
-/* The whole backward of the audio conv2 layer in one launch (lbwd.hip; CentralUnimodalAudio
- * conv2 -> bn2 -> ReLU -> MaxPool2d, unimodal.py:185-221: 56x56, Cin 8 -> Cout 16, 5x5 pad 2,
- * bf16): from y [N][56][56][16] and the pooled gradient gout [N][28][28][16] (layout 0) with
+/* The whole backward of one audio conv layer in one launch (lbwd.hip; CentralUnimodalAudio
+ * conv -> bn -> ReLU -> MaxPool2d, unimodal.py:185-221).  Two shapes are served, both 5x5 pad 2,
+ * bf16, H = W:
+ *   conv2: 56x56, Cin 8  -> Cout 16        conv3: 28x28, Cin 16 -> Cout 32
+ * every other shape (28x20, 20x28, other channel counts, ...) is declined: the slab query
+ * answers 0 and a launch returns AVD_ERR_SHAPE before anything is written.  From y [N][H][W][Cout]
+ * and the pooled gradient gout [N][H/2][W/2][Cout] (layout 0) with
  * avd_bn_finalize's scale / shift and avd_bn_bwd_finalize's coef -- or, with y == NULL, from a
  * given dy -- it forms dy exactly as avd_cl_bn_bwd_apply (never stored), and from each staged dy
  * tile both
- *   dx [N][56][56][8]   = the input gradient, bit-identical to avd_cl_conv_dgrad (wk_d: the
- *                         avd_cl_weight_layout(..., dgrad = 1) rows), and
- *   parts[s][16*8*25]   = per-slab partial dW (sum with avd_sum_rows over `slabs` rows).
+ *   dx [N][H][W][Cin]       = the input gradient, bit-identical to avd_cl_conv_dgrad (wk_d: the
+ *                             avd_cl_weight_layout(..., dgrad = 1) rows), and
+ *   parts[s][Cout*Cin*25]   = per-slab partial dW (sum with avd_sum_rows over `slabs` rows).
  * Replaces avd_cl_bn_bwd_apply + avd_cl_conv_dgrad + avd_cl_conv_wgrad for that layer.  `slabs`
  * is the grid: pass the avd_cl_layer_bwd_slabs() value the parts buffer was sized with (0: the
  * shape is not served).  N / B <= 8 BN groups when y is given. */

@@ -129,22 +129,29 @@ class ConvBranch:
         # not divide the batch (an odd last batch) runs on the bf16 kernels.
         self.fp8 = bool(fp8) and act_dtype == torch.bfloat16
 
-    # fp8 (config 5): a layer the fused bf16 layer backward serves (the audio conv2, 56^2) keeps
+    # fp8 (config 5): the audio conv2 (56^2), which the fused bf16 layer backward serves, keeps
     # its input and weight gradient in bf16 through that one launch; its forward stays MX
-    # (16.7-17.0 vs 17.4-17.8 ms per B = 4096 step, profiles/r6_ab_fp8_fused_bwd.txt)
+    # (16.7-17.0 vs 17.4-17.8 ms per B = 4096 step, profiles/r6_ab_fp8_fused_bwd.txt).  The other
+    # fused shape (the 28^2 layer) stays on its MX kernels: no config-5 measurement says otherwise.
     FP8_FUSED_BWD = True
+    FP8_FUSED_H = 56
 
-    def _fused_bwd(self, i, N):
+    def _fused_bwd(self, i, N, B=None):
+        """fp8: layer i leaves its MX backward kernels for the fused bf16 launch.  The same
+        conditions as _layer_bwd_slabs (pooled gradient in layout 0, at most APPLY_GMAX groups
+        where the group size is known), so the MX-layout choice and the launch choice agree."""
         ci, co, k, p = self.stack.convs[i]
         H = self.dims[i][0]
-        return (self.FP8_FUSED_BWD and self.LAYER_BWD and i > 0
+        mode = self._tail_mode() if i == len(self.stack.convs) - 1 else 0
+        return (self.FP8_FUSED_BWD and self.LAYER_BWD and i > 0 and H == self.FP8_FUSED_H
+                and mode == 0 and (B is None or N // B <= ops.APPLY_GMAX)
                 and ops.cl_layer_bwd_slabs(self.act, N, ci, H, H, co, k, p) > 0)
 
     def _mx_ok(self, i, N, B=None, dgrad=False):
         """MX kernel for layer i's forward (B: the BN group size when it writes partials) or
         input gradient over N samples."""
         ci, co, k, p = self.stack.convs[i]
-        return (self.fp8 and i > 0 and not (dgrad and self._fused_bwd(i, N))
+        return (self.fp8 and i > 0 and not (dgrad and self._fused_bwd(i, N, B))
                 and ops.mx_conv_serves(ci, self.dims[i][0], co, k, p, dgrad, N, None if dgrad else B))
 
     def prepare(self, ws, store, tag, need_dgrad, N, B=None, launch=True):
@@ -165,7 +172,7 @@ class ConvBranch:
                 wk = ws.get(f"{tag}.wk{i}", ops.cl_weight_elems(co, ci, k, 0), self.act)
                 batch.append((w, wk, 0))
             if need_dgrad and i > 0:
-                if self._mx_ok(i, N, dgrad=True):
+                if self._mx_ok(i, N, B, dgrad=True):
                     qd = (ws.get(f"{tag}.wqd{i}", ops.mx_weight_bytes(co, ci, k, 1), torch.uint8),
                           ws.get(f"{tag}.wqds{i}", ops.mx_scale_bytes(co, ci, k, 1), torch.uint8))
                     mxb.append((w, qd[0], qd[1], 1))
@@ -194,21 +201,21 @@ class ConvBranch:
         else:
             ops.cl_conv_dgrad(dy, wt[1], dx, N, ci, H, H, co, k, pad)
 
-    def _mx_wgrad(self, i, N):
+    def _mx_wgrad(self, i, N, B=None):
         ci, co, k, p = self.stack.convs[i]
-        return (self.fp8 and i > 0 and not self._fused_bwd(i, N)
+        return (self.fp8 and i > 0 and not self._fused_bwd(i, N, B)
                 and ops.mx_wgrad_chunks(N, ci, self.dims[i][0], co, k, p) > 0)
 
-    def _wgrad_chunks(self, i, N):
+    def _wgrad_chunks(self, i, N, B=None):
         ci, co, k, p = self.stack.convs[i]
-        if self._mx_wgrad(i, N):
+        if self._mx_wgrad(i, N, B):
             return ops.mx_wgrad_chunks(N, ci, self.dims[i][0], co, k, p)
         return ops.cl_wgrad_chunks(N, co, ci, k)
 
-    def _conv_wgrad(self, i, x, dy, wparts, N):
+    def _conv_wgrad(self, i, x, dy, wparts, N, B=None):
         ci, co, k, pad = self.stack.convs[i]
         H = self.dims[i][0]
-        if self._mx_wgrad(i, N):
+        if self._mx_wgrad(i, N, B):
             ops.mx_conv_wgrad(x, dy, wparts, N, ci, H, H, co, k, pad)
         else:
             ops.cl_conv_wgrad(x, dy, wparts, N, ci, H, H, co, k, pad)
@@ -561,15 +568,31 @@ class ConvBranch:
     # weight-gradient stream is given: the audio 14^2 layer (its launch ran 640-650 us in the
     # graph beside two other streams' kernels, 153 us alone).  Round 6, with the fused 56^2 layer
     # backward, three interleaved rounds (profiles/r6_ab_wgrad_main.txt): {3} 4.913-4.936 ms,
-    # none 4.911-4.957, {2} 4.973-5.004, {2, 3} (round 5's choice) 4.991-5.031
+    # none 4.911-4.957, {2} 4.973-5.004, {2, 3} (round 5's choice) 4.991-5.031.  With the 28^2
+    # layer fused too (its weight gradient gone from the side stream; profiles/lbwd28_ab.txt):
+    # {3} 4.393-4.396 ms, none 4.572-4.589 (the 14^2 weight gradient then runs beside the fused
+    # 28^2 launch and costs that launch's whole gain)
     WGRAD_MAIN = frozenset({3})
 
     # the audio conv2 (56^2) backward as ONE launch (avd_cl_layer_bwd: BN-backward apply, input
     # and weight gradient from the same staged tiles, no dY in HBM); False: apply + dgrad + wgrad
     LAYER_BWD = True
-    # that launch routes the pooled gradient by the forward pool's argmax codes
+    # the same launch for the audio conv3 (28^2, 16 -> 32): a switch of its own, so LAYER_BWD
+    # still toggles the 56^2 layer alone
+    LAYER_BWD_28 = True
+    # those launches route the pooled gradient by the forward pool's argmax codes
     # (avd_cl_bn_relu_pool_codes) instead of recomputing relu(bn(y)) per window; False: recompute
     LAYER_BWD_CODES = True
+
+    def _layer_bwd_on(self, i):
+        """The class switch of layer i's fused launch (by its input map: 28^2 or 56^2)."""
+        return self.LAYER_BWD_28 if self.dims[i][0] == 28 else self.LAYER_BWD
+
+    @staticmethod
+    def _lb_dx_name(n):
+        """dX buffer of the n-th fused launch of a backward pass: consecutive fused layers
+        alternate, since each one's pooled gradient is the dX the one before it wrote."""
+        return "bwd_dx_lb" if n % 2 == 0 else "bwd_dx_lb1"
 
     def _layer_bwd_slabs(self, i, N, B, mode, wt):
         """Slabs of layer i's fused backward launch, 0 where the layer takes the separate
@@ -578,8 +601,8 @@ class ConvBranch:
         coefficients, e.g. not 2 + 7 views.)"""
         ci, co, k, pad = self.stack.convs[i]
         H = self.dims[i][0]
-        if not (self.LAYER_BWD and i > 0 and mode == 0 and wt[1] is not None and wt[3] is None
-                and N // B <= ops.APPLY_GMAX and not self._mx_wgrad(i, N)):
+        if not (self._layer_bwd_on(i) and i > 0 and mode == 0 and wt[1] is not None and wt[3] is None
+                and N // B <= ops.APPLY_GMAX and not self._mx_wgrad(i, N, B)):
             return 0
         return ops.cl_layer_bwd_slabs(self.act, N, ci, H, H, co, k, pad)
 
@@ -594,6 +617,7 @@ class ConvBranch:
         nl = len(self.stack.convs)
         main = torch.cuda.current_stream(dfeat.device) if wstream is not None else None
         wdone = []
+        nlb = 0                        # fused layer launches so far
         for i in reversed(range(nl)):
             ci, co, k, pad = self.stack.convs[i]
             H, Ho, Hp = self.dims[i]
@@ -622,10 +646,11 @@ class ConvBranch:
             lbs = self._layer_bwd_slabs(i, N, B, mode, wt)
             if lbs:
                 # the whole layer backward in one launch: dY formed in LDS from y and the pooled
-                # gradient, dX and the dW slabs from the same tiles (lbwd.hip); its own dX
-                # buffer, since gout is the previous dgrad's "bwd_dx"
+                # gradient, dX and the dW slabs from the same tiles (lbwd.hip); a dX buffer
+                # that is neither the previous dgrad's "bwd_dx" nor the previous fused launch's
                 wparts = ws.get(f"lb_parts{i}", lbs * co * ci * k * k)
-                dx = ws.get("bwd_dx_lb", N * H * H * ci, self.act)
+                dx = ws.get(self._lb_dx_name(nlb), N * H * H * ci, self.act)
+                nlb += 1
                 ops.mark(f"w{i}.begin")
                 ops.cl_layer_bwd(y, gout, st[2], st[3], coef, None, x, wt[1], dx, wparts, lbs, N, B, ci,
                                  H, H, co, k, pad, codes=ctx["pool_codes"].get(i))
@@ -642,7 +667,7 @@ class ConvBranch:
                 ops.sum_rows(wparts, nsl, co * ci * k * k, store.grad_of(ck + ".weight"))
                 ops.mark(f"b{i}")
                 continue
-            nch = self._wgrad_chunks(i, N)
+            nch = self._wgrad_chunks(i, N, B)
             dy = ws.get(f"bwd_dy{i}" if wstream is not None else "bwd_dy", N * Ho * Ho * co, self.act)
             ops.cl_bn_bwd_apply(y, gout, mode, st[2], st[3], coef, dy, N, B, co, Ho, Ho)
             if wstream is not None and i > 0 and i not in self.WGRAD_MAIN:
@@ -650,7 +675,7 @@ class ConvBranch:
                 wstream.wait_stream(main)
                 with torch.cuda.stream(wstream):
                     ops.mark(f"w{i}.begin")
-                    self._conv_wgrad(i, x, dy, wparts, N)
+                    self._conv_wgrad(i, x, dy, wparts, N, B)
                     ops.sum_rows(wparts, nch, co * ci * k * k, store.grad_of(ck + ".weight"))
                     ops.mark(f"w{i}.end")
                     ev = new_event()
@@ -659,7 +684,7 @@ class ConvBranch:
             else:
                 wparts = ws.get("wgrad_parts", nch * co * ci * k * k)
                 ops.mark(f"w{i}.begin")
-                self._conv_wgrad(i, x, dy, wparts, N)
+                self._conv_wgrad(i, x, dy, wparts, N, B)
                 ops.sum_rows(wparts, nch, co * ci * k * k, store.grad_of(ck + ".weight"))
                 ops.mark(f"w{i}.end")
             if i > 0:

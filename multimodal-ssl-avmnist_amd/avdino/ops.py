@@ -642,13 +642,16 @@ APPLY_GMAX = 8          # BN groups a fused BN-backward apply serves (csrc/bnapp
 
 def cl_layer_bwd_slabs(dtype, N, Cin, H, W, Cout, K, pad):
     """Slabs (= grid) of the fused layer backward (avd_cl_layer_bwd), 0 if the shape is not
-    served (the audio conv2: 56^2, 8 -> 16, 5x5 pad 2, bf16)."""
+    served.  Served, both 5x5 pad 2, bf16, H == W: the audio conv2 (56^2, 8 -> 16) and the audio
+    conv3 (28^2, 16 -> 32)."""
     return lib.avd_cl_layer_bwd_slabs(_DT[dtype], N, Cin, H, W, Cout, K, pad)
 
 
 def cl_layer_bwd(y, gout, scale, shift, coef, dy, x, wk_d, dx, parts, slabs, N, B, Cin, H, W, Cout,
                  K, pad, codes=None):
-    """The whole backward of one conv layer in one launch (lbwd.hip): dY formed from y and the
+    """The whole backward of one conv layer in one launch (lbwd.hip; the two shapes of
+    cl_layer_bwd_slabs: 56^2 8 -> 16 and 28^2 16 -> 32, anything else raises AVD_ERR_SHAPE before a
+    launch): dY formed from y and the
     pooled gradient (or taken from ``dy`` when y is None) in LDS only, dX (bit-identical to
     cl_conv_dgrad) and the weight-gradient slabs parts[slabs][Cout*Cin*K*K] (sum_rows).
     ``codes``: the forward's cl_bn_relu_pool_codes words of this y -- the gradient is routed by

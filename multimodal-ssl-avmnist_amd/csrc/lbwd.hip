@@ -23,6 +23,19 @@
 //     in registers across all of the block's tiles; the four waves split the pixels and are
 //     summed through LDS at the end; one deterministic f32 slab per block (avd_sum_rows).
 // HBM per launch: y + pooled gradient + X read once, dX written once (1.6 GB at N = 7168), no dY.
+//
+// Second instantiation: the audio conv3 layer (28x28, 16 -> 32, 5x5 pad 2), LbA3 (0.86 GB per
+// launch at N = 7168 for what were 2.0 GB in three launches).  What differs:
+//   * rows are 28 pixels, so the weight gradient's 32-pixel k-steps are one row padded to W8 = 32
+//     (WgA3's map, wgrad_ws.hip): the dY image keeps its pad columns zero for the whole launch and
+//     the X image is W8 + 4 columns wide, zero past the map;
+//   * the dY pixel stride is 48 elements (DgrA3's / WgA3's conflict-free image), the input
+//     gradient's k-step is one tap x 32 dY channels in DgrA3's order (bit-identical dX), its D
+//     tile is full (16 dX channels, no row pairs), and its 16-pixel groups cross row ends;
+//   * 25 resident weight fragments (100 VGPRs) beside 2 x 25 dW accumulator tiles do not fit one
+//     wave at two blocks per CU, so the waves specialise (SP): waves 0-1 run the input gradient,
+//     waves 2-3 the weight gradient (13 column tiles x 2 row tiles each), and the resident
+//     weights / the accumulators share one register array; all four waves stage.
 #include <algorithm>
 #include <type_traits>
 
@@ -43,6 +56,12 @@ __device__ const u4 kZeroL = {0u, 0u, 0u, 0u};
 
 constexpr int cdv(int a, int b) { return (a + b - 1) / b; }
 
+// LBWD28_PFD, LBWD28_GB, LBWD28_WFD (build-time, for A/B builds of the 28^2 instantiation): the
+// input gradient's read-ahead depth and groups per pass, the weight gradient's ring depth
+#ifndef LBWD28_WFD
+#define LBWD28_WFD 3
+#endif
+
 template <int V> using IC = std::integral_constant<int, V>;
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -52,17 +71,22 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-template <int TH_, int OCC_, int PFD_ = 6, int GB_ = 1, int NCW_ = 1, int RP_ = 0, int BAL_ = 0, int WGU_ = 0>
+template <int CIN_, int COUT_, int H_, int W_, int TH_, int OCC_, int PFD_ = 6, int GB_ = 1, int NCW_ = 1,
+          int RP_ = 0, int BAL_ = 0, int WGU_ = 0, int SP_ = 0>
 struct Lb {
-  static constexpr int CIN = 8, COUT = 16, K = 5, PAD = 2, H = 56, W = 56;   // the forward conv
+  static constexpr int CIN = CIN_, COUT = COUT_, K = 5, PAD = 2, H = H_, W = W_;   // the forward conv
+  static constexpr int OCT = COUT / 8, XOCT = CIN / 8;          // 16-byte vectors per pixel
+  static constexpr int W8 = (W + 7) & ~7;                       // weight-gradient row (8-pixel runs)
   static constexpr int TH = TH_, TPS = H / TH, OCC = OCC_, PFD = PFD_, GB = GB_;
   static constexpr int ITH = TH + K - 1, ITW = W + K - 1;        // staged rows / columns (halo)
   // dY tile [ITH][RS][PS]: DgrA2's conflict-free image (pixel stride 16 channels, rows padded
   // by 4 pixels); X tile [ITH][XW][XS]: WgA2's
-  static constexpr int PS = COUT, RS = ITW + 4, XW = ITW, XS = CIN;
+  // (32 channels: DgrA3's / WgA3's 48-element pixel stride; X rows reach W8 + K - 1 columns so
+  // the padded pixels of a weight-gradient row read zeros, not stale LDS)
+  static constexpr int PS = COUT <= 16 ? COUT : COUT + 16, RS = ITW + 4, XW = W8 + K - 1, XS = CIN;
   static constexpr int DY_ELEMS = ITH * RS * PS, X_ELEMS = ITH * XW * XS;
-  // input gradient: M = dX channels (8 rows of a 16-row tile), N = 16-pixel groups,
-  // K = (tap, dY channel) in conv_ws's order, 13 k-steps of 32
+  // input gradient: M = dX channels (8 rows of a 16-row tile, or all 16), N = 16-pixel groups,
+  // K = (tap, dY channel) in conv_ws's order, 13 k-steps of 32 (32 dY channels: 25, one per tap)
   static constexpr int KK = K * K, KPAD = cdv(KK * COUT, 32) * 32;
   // RP (row pairs): one MFMA row tile = dX channels of TWO output rows (m < 8: row y, m >= 8: row
   // y + 1) over the 6 x 5 dY taps both rows need -- 15 k-steps per 16 pixels of a row pair
@@ -70,34 +94,46 @@ struct Lb {
   // k-step reads a 16-byte im2col fragment per lane)
   static constexpr int RP = RP_, KTAPS = RP ? (K + 1) * K : KK;
   static constexpr int KS = cdv(KTAPS * COUT, 32);
-  static constexpr int PIX = TH * W, NG = (RP ? PIX / 2 : PIX) / 16, GW = cdv(NG, 4);
+  // SP (specialised waves): waves [0, 2) run the input gradient, waves [2, 4) the weight
+  // gradient; otherwise all four run both
+  static constexpr int SP = SP_, NDW = SP ? 2 : 4, NWW = SP ? 2 : 4;
+  static constexpr int PIX = TH * W, NG = (RP ? PIX / 2 : PIX) / 16, GW = cdv(NG, NDW);
   // weight gradient: 13 column tiles (tap pair x 8 channels), K = PIX pixels in 32-pixel steps;
   // the 4 waves split NCW ways over column tiles (NW per wave) and NPW = 4 / NCW over k-steps
-  static constexpr int NCT = cdv(KK, 2), WKS = PIX / 32;
-  static constexpr int NCW = NCW_, NW = cdv(NCT, NCW), NPW = 4 / NCW;
-  static constexpr int WT = (ITH / 2) * (ITW / 2) * (COUT / 8);   // AP: window x channel-half tasks
+  // (16 X channels: 25 column tiles, one tap x 16 channels each; MT row tiles of 16 dY channels)
+  static constexpr int MT = COUT / 16, NCT = CIN == 8 ? cdv(KK, 2) : KK, WKS = TH * W8 / 32;
+  static constexpr int NCW = NCW_, NW = cdv(NCT, NCW), NPW = NWW / NCW;
+  static constexpr int WT = (ITH / 2) * (ITW / 2) * OCT;          // AP: window x channel-octet tasks
   // BAL (balanced apply staging): slot 0 = the tasks of the TH / 2 window rows a continuation
   // tile forms anew (NEWT, spread over all four waves), slot 1 = the PAD window rows it copies
   // from the previous tile (OLDT) -- a continuation tile runs slot 0 only.  Without BAL the
   // tasks sit in linear order on the two slots, and in a continuation tile one wave has live
   // lanes in both and runs the apply twice while the other three wait at the barrier.
   static constexpr int BAL = BAL_;
-  static constexpr int NEWT = (TH / 2) * (ITW / 2) * (COUT / 8), OLDT = WT - NEWT;
+  static constexpr int NEWT = (TH / 2) * (ITW / 2) * OCT, OLDT = WT - NEWT;
   static_assert(!BAL || (NEWT <= 256 && OLDT <= 256), "balanced staging: one slot each");
-  // WGU: the weight gradient's k-step loop unrolled, each k-step's pixel origin a constant
-  static constexpr int WGU = WGU_;
+  // WGU: the weight gradient's k-step loop unrolled, each k-step's pixel origin a constant;
+  // 2: also one fragment ring over all (k-step, column tile) pairs of the tile, WFD reads ahead
+  // (13 column tiles per wave: two whole k-steps of fragments would not fit the registers)
+  static constexpr int WGU = WGU_, WFD = LBWD28_WFD;
   static_assert(!WGU || NPW == 1, "unrolled weight gradient: every wave walks all k-steps");
-  static constexpr int DT = ITH * ITW * (COUT / 8);               // AP = 0: 16-byte dY tasks
-  static constexpr int XT = ITH * ITW * (CIN / 8);                // 16-byte X tasks
-  static constexpr int RED = (NPW - 1) * NCW * NW * 64;           // f4 slots: pixel partials
+  static_assert(WGU != 2 || W8 == 32, "fragment ring: one k-step = one padded row");
+  static constexpr int DT = ITH * ITW * OCT;                      // AP = 0: 16-byte dY tasks
+  static constexpr int XT = ITH * XW * XOCT;                      // 16-byte X tasks
+  static constexpr int RED = (NPW - 1) * NCW * NW * MT * 64;      // f4 slots: pixel partials
   // two tile images (double buffer): tile i + 1 is staged while tile i's MFMAs run, one barrier
   // per tile (the apply's VALU work beside the MFMAs instead of between two barriers)
   static constexpr int BUF = DY_ELEMS + X_ELEMS;
   static constexpr int SMEM = 2 * BUF > RED * 8 ? 2 * BUF : RED * 8;
-  static_assert(H % TH == 0 && TH % 2 == 0 && PIX % 32 == 0 && PIX % 16 == 0, "tiles");
+  static_assert((CIN == 8 && COUT == 16) || (CIN == 16 && COUT == 32), "k-group and column maps");
+  static_assert(H % TH == 0 && TH % 2 == 0 && (TH * W8) % 32 == 0 && PIX % 16 == 0, "tiles");
+  static_assert(TH >= 2 * PAD && W8 + PAD <= RS, "continuation rows, padded weight-gradient row");
   static_assert(SMEM * 2 <= 76 * 1024, "LDS (two blocks per CU: 160 KB)");
-  static_assert(4 % NCW == 0, "wave split");
-  static_assert(!RP || (KTAPS * COUT) % 32 == 0, "row-pair k-steps");
+  static_assert(NWW % NCW == 0, "wave split");
+  static_assert(!RP || (CIN == 8 && (KTAPS * COUT) % 32 == 0), "row-pair k-steps");
+  // SP: the resident weights (input-gradient waves) and the accumulators (weight-gradient waves)
+  // are one register array
+  static_assert(!SP || (KS <= MT * NW && NPW == 1), "specialised waves: shared registers");
 };
 
 __device__ __forceinline__ u2 tr4(const bf16* p) {
@@ -183,11 +219,43 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
   };
   const int tid = threadIdx.x, wp = tid >> 6, lane = tid & 63;
   const int g = lane >> 4, r16 = lane & 15, q4 = r16 >> 2, p4 = r16 & 3;
-  const int wc = wp / L::NPW, wq = wp % L::NPW;     // weight gradient: column group, pixel part
+  // SP: the wave's role (wave-uniform, so the role branches are scalar) and its index in the role
+  const bool dgw = !L::SP || __builtin_amdgcn_readfirstlane(wp) < L::NDW;
+  const bool wgw = !L::SP || !dgw;
+  const int dwp = L::SP ? (wp & (L::NDW - 1)) : wp, wwp = L::SP ? (wp & (L::NWW - 1)) : wp;
+  const int wc = wwp / L::NPW, wq = wwp % L::NPW;   // weight gradient: column group, pixel part
 
-  // ---- input-gradient weights (flipped, [16 rows][KPAD], rows 8-15 zero), resident
-  bf16x8 a[L::KS];
-  if constexpr (L::RP) {
+  // dY pad columns (a padded weight-gradient row reads PAD pixels past the halo): zero in both
+  // buffers for the whole launch -- nothing stages them, and a continuation copy moves zeros
+  if constexpr (L::W8 != L::W) {
+    constexpr int PC = L::RS - L::ITW, CH = L::PS / 8;
+    for (int i = tid; i < 2 * L::ITH * PC * CH; i += 256) {
+      const int q = i % CH, t = i / CH, c = L::ITW + t % PC, rb = t / PC;
+      const int b = rb / L::ITH, r = rb - b * L::ITH;
+      *reinterpret_cast<u4*>(smem + b * L::BUF + (r * L::RS + c) * L::PS + 8 * q) = u4{0u, 0u, 0u, 0u};
+    }
+  }
+
+  // ---- weight-gradient accumulators; SP: in the input-gradient waves the same registers hold
+  // the resident weights (wa)
+  f4 wacc[L::MT * L::NW];
+  // ---- input-gradient weights (flipped, [16 rows][KPAD]; 8 dX channels: rows 8-15 zero), resident
+  bf16x8 a[L::SP ? 1 : L::KS];
+  auto wa = [&](auto jc) -> bf16x8 {
+    constexpr int j = decltype(jc)::value;
+    if constexpr (L::SP) return __builtin_bit_cast(bf16x8, wacc[j]);
+    else return a[j];
+  };
+  if constexpr (L::SP) {
+    if (dgw) {
+#pragma unroll
+      for (int j = 0; j < L::KS; ++j)
+        wacc[j] = __builtin_bit_cast(f4, *reinterpret_cast<const bf16x8*>(wk + (size_t)r16 * L::KPAD + 32 * j + 8 * g));
+    } else {
+#pragma unroll
+      for (int j = 0; j < L::MT * L::NW; ++j) wacc[j] = f4{0.f, 0.f, 0.f, 0.f};
+    }
+  } else if constexpr (L::RP) {
     // row m = (output row m >> 3, dX channel m & 7); k-group 4 j + g = staged-row offset /
     // filter column t = 2 j + (g >> 1) of the 6 x 5 window, dY channel half 8 (g & 1): the
     // filter row is t / 5 - (m >> 3) -- outside [0, 5) the weight is 0
@@ -205,7 +273,8 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
   }
   // k-group (ks, g) = taps 2 ks (g < 2) / 2 ks + 1 (g >= 2), channel half g & 1: the k-step part
   // of its offset is a compile-time immediate (tapoff), the lane part one of three registers
-  const int ln_a = (g >> 1) * L::PS + 8 * (g & 1);                  // tap + 1 on the same row
+  // (32 dY channels, DgrA3's order: k-step j = tap j, the lane's k-group its channel octet g)
+  const int ln_a = L::COUT == 32 ? 8 * g : (g >> 1) * L::PS + 8 * (g & 1);   // tap + 1 on the same row
   const int ln_b = (g >> 1) * (L::RS - (L::K - 1)) * L::PS + 8 * (g & 1);   // next filter row
   const int ln_c = (g >> 1) ? -tapoff<L>(L::KK - 1) : 8 * (g & 1);  // past the last tap: tap 0
 
@@ -213,14 +282,15 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
   int xo[L::NW];
 #pragma unroll
   for (int j = 0; j < L::NW; ++j) {
-    int tap = 2 * (wc * L::NW + j) + (p4 >> 1);
-    const int ch = 4 * (p4 & 1);
+    int tap = L::CIN == 8 ? 2 * (wc * L::NW + j) + (p4 >> 1) : wc * L::NW + j;
+    const int ch = L::CIN == 8 ? 4 * (p4 & 1) : 4 * p4;
     if (tap >= L::KK) tap = 0;
     xo[j] = ((tap / L::K) * L::XW + tap % L::K) * L::XS + ch;
   }
-  f4 wacc[L::NW];
+  if constexpr (!L::SP) {
 #pragma unroll
-  for (int j = 0; j < L::NW; ++j) wacc[j] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < L::MT * L::NW; ++j) wacc[j] = f4{0.f, 0.f, 0.f, 0.f};
+  }
 
   // ---- contiguous tile range of this block (tile = TH rows of one sample)
   const int per = ntiles / (int)gridDim.x, extra = ntiles % (int)gridDim.x;
@@ -241,7 +311,7 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
 #pragma unroll
   for (int i = 0; i < YSL; ++i) {
     const int task = ytask(i);
-    const int q = task & 1, w = task >> 1;             // COUT / 8 = 2 channel halves
+    const int q = task & (L::OCT - 1), w = task / L::OCT;   // COUT / 8 = 2 or 4 channel octets
     if constexpr (AP) {
       const int wc2 = w % (L::ITW / 2), wr = w / (L::ITW / 2);
       const int r = 2 * wr, c = 2 * wc2, ix = c - L::PAD;
@@ -260,10 +330,11 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
 #pragma unroll
   for (int i = 0; i < XSL; ++i) {
     const int task = tid + 256 * i;
-    const int c = task % L::ITW, r = task / L::ITW, ix = c - L::PAD;
+    const int q = task & (L::XOCT - 1), px = task / L::XOCT;
+    const int c = px % L::XW, r = px / L::XW, ix = c - L::PAD;
     xrow[i] = r;
-    xlo[i] = (r * L::XW + c) * L::XS;
-    xgo[i] = (task < L::XT && ix >= 0 && ix < L::W) ? (r * L::W + ix) * L::CIN : -1;
+    xlo[i] = (r * L::XW + c) * L::XS + 8 * q;
+    xgo[i] = (task < L::XT && ix >= 0 && ix < L::W) ? (r * L::W + ix) * L::CIN + 8 * q : -1;
   }
   if constexpr (AP == 1) apply_load_ctab<L::COUT>(ctab, aa, tid, 256);
   if constexpr (AP == 2) apply_load_ktab<L::COUT>(ctab, aa, tid, 256);
@@ -329,7 +400,7 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
       if constexpr (AP) {
         u4 o[4] = {u4{0u, 0u, 0u, 0u}, u4{0u, 0u, 0u, 0u}, u4{0u, 0u, 0u, 0u}, u4{0u, 0u, 0u, 0u}};
         if (ygo[i] >= 0 && (unsigned)(ty0 - L::PAD + yrow[i]) < (unsigned)L::H) {
-          const float* ct = ctab + (n / aa.B) * CTR * L::COUT + 8 * (task & 1);
+          const float* ct = ctab + (n / aa.B) * CTR * L::COUT + 8 * (task & (L::OCT - 1));
           if constexpr (AP == 2) apply_window_codes(wpre[i], ct, L::COUT, o);
           else apply_window_lean(wpre[i], ct, L::COUT, o);
         }
@@ -356,7 +427,7 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
       bool gv[L::GB];
 #pragma unroll
       for (int b = 0; b < L::GB; ++b) {
-        const int grp = wp + 4 * (i0 + b);
+        const int grp = dwp + L::NDW * (i0 + b);
         const int p = grp * 16 + r16;
         gv[b] = i0 + b < L::GW && grp < L::NG;
         int ry = p / L::W;
@@ -375,6 +446,12 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
       auto ld = [&](bf16x8 (&dst)[L::GB], auto jc) {
         constexpr int J = decltype(jc)::value;
         constexpr int t0 = 2 * J;
+        if constexpr (L::COUT == 32) {
+#pragma unroll
+          for (int b = 0; b < L::GB; ++b)
+            dst[b] = *reinterpret_cast<const bf16x8*>(dys + base[b] + ln_a + tapoff<L>(J));
+          return;
+        }
         const int ln = (!L::RP && t0 + 1 >= L::KK) ? ln_c : ((t0 % L::K) == L::K - 1 ? ln_b : ln_a);
 #pragma unroll
         for (int b = 0; b < L::GB; ++b)
@@ -389,12 +466,19 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
         if constexpr (j + PF < L::KS) ld(bq[(j + PF) % (PF + 1)], IC<j + PF>{});
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int b = 0; b < L::GB; ++b) acc[b] = mma(a[j], bq[j % (PF + 1)][b], acc[b]);
+        for (int b = 0; b < L::GB; ++b) acc[b] = mma(wa(jc), bq[j % (PF + 1)][b], acc[b]);
         __builtin_amdgcn_sched_barrier(0);
       });
       // rows 4g..4g+3 of the D tile: dX channels 4 (g & 1).. of row y (g < 2) or, with RP, of
       // row y + 1 (g >= 2); without RP rows 8-15 are padding
-      if (L::RP || g < 2) {
+      if constexpr (L::CIN == 16) {     // a full D tile: dX channels 4 g .. 4 g + 3 of the lane's pixel
+#pragma unroll
+        for (int b = 0; b < L::GB; ++b) {
+          if (!gv[b]) continue;
+          const uint32_t lo = pack_bf16x2(acc[b][0], acc[b][1]), hi = pack_bf16x2(acc[b][2], acc[b][3]);
+          *reinterpret_cast<uint2*>(dx + (size_t)opix[b] * L::CIN + 4 * g) = make_uint2(lo, hi);
+        }
+      } else if (L::RP || g < 2) {
 #pragma unroll
         for (int b = 0; b < L::GB; ++b) {
           if (!gv[b]) continue;
@@ -452,6 +536,42 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
   };
   // the tile's interior pixel P (row P / W, column P % W) sits at dY tile row + PAD, column + PAD
   auto wgrad_tile = [&]() {
+    if constexpr (L::WGU == 2) {
+      // step s = (k-step s / NW = the tile's padded row, column tile s % NW): B fragments WFD
+      // steps ahead of their MFMAs across k-step ends, the next row's MT A fragments read at the
+      // row's first step; WgA3's pixel and column maps (kpix, xo)
+      constexpr int S = L::WKS * L::NW, PF = L::WFD;
+      u2 af[2][L::MT][2], bq[PF + 1][2];
+      auto ld_a = [&](auto ksc, u2 (&dst)[L::MT][2]) {
+        constexpr int cpa = ((decltype(ksc)::value + L::PAD) * L::RS + L::PAD) * L::PS;
+#pragma unroll
+        for (int m = 0; m < L::MT; ++m) {
+          dst[m][0] = tr4(dys + lpa + (cpa + 16 * m));
+          dst[m][1] = tr4(dys + lpa + (cpa + 16 * m + 8 * L::PS));
+        }
+      };
+      auto ld_b = [&](auto sc, u2 (&dst)[2]) {
+        constexpr int ks = decltype(sc)::value / L::NW, j = decltype(sc)::value % L::NW;
+        constexpr int cxb = ks * L::XW * L::XS;
+        dst[0] = tr4(xs + lxo[j] + cxb);
+        dst[1] = tr4(xs + lxo[j] + (cxb + 8 * L::XS));
+      };
+      ld_a(IC<0>{}, af[0]);
+      static_for<0, (PF < S ? PF : S)>([&](auto sc) { ld_b(sc, bq[decltype(sc)::value]); });
+      static_for<0, S>([&](auto sc) {
+        constexpr int s = decltype(sc)::value, ks = s / L::NW, j = s % L::NW;
+        if constexpr (s + PF < S) ld_b(IC<s + PF>{}, bq[(s + PF) % (PF + 1)]);
+        if constexpr (j == 0 && ks + 1 < L::WKS) ld_a(IC<ks + 1>{}, af[(ks + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+        const bf16x8 b8 = frag8(bq[s % (PF + 1)][0], bq[s % (PF + 1)][1]);
+#pragma unroll
+        for (int m = 0; m < L::MT; ++m)
+          wacc[m * L::NW + j] = mma(frag8(af[ks & 1][m][0], af[ks & 1][m][1]), b8, wacc[m * L::NW + j]);
+        __builtin_amdgcn_sched_barrier(0);
+      });
+      return;
+    }
+    static_assert(L::WGU == 2 || L::MT == 1, "the k-step-buffered loops hold one A fragment");
     if constexpr (L::WGU) {
       u2 af[2][2], bb[2][L::NW][2];
       wg_load_c(IC<0>{}, af[0], bb[0]);
@@ -496,8 +616,8 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
     for (int ti = t0; ti < t1; ++ti) {
       const int b = (ti - t0) & 1;
       set_buf(b);
-      dgrad_tile(ti);
-      wgrad_tile();
+      if (dgw) dgrad_tile(ti);
+      if (wgw) wgrad_tile();
       if (ti + 1 < t1) {
         const bf16* pd = dys;     // tile ti's images: its last rows may seed tile ti + 1
         const bf16* px = xs;
@@ -512,28 +632,33 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
   // ---- pixel-split dW partials -> wave 0 (fixed order), slab [co][ci][tap] through LDS
   f4* red = reinterpret_cast<f4*>(smem);
   __syncthreads();
-  if (wq > 0) {
+  constexpr int NA = L::MT * L::NW;
+  if (wgw && wq > 0) {
 #pragma unroll
-    for (int j = 0; j < L::NW; ++j) red[(((wq - 1) * L::NCW + wc) * L::NW + j) * 64 + lane] = wacc[j];
+    for (int j = 0; j < NA; ++j) red[(((wq - 1) * L::NCW + wc) * NA + j) * 64 + lane] = wacc[j];
   }
   __syncthreads();
-  if (wq == 0) {
+  if (wgw && wq == 0) {
 #pragma unroll
     for (int w = 1; w < L::NPW; ++w)
 #pragma unroll
-      for (int j = 0; j < L::NW; ++j) wacc[j] += red[(((w - 1) * L::NCW + wc) * L::NW + j) * 64 + lane];
+      for (int j = 0; j < NA; ++j) wacc[j] += red[(((w - 1) * L::NCW + wc) * NA + j) * 64 + lane];
   }
   __syncthreads();
   constexpr int PER_CO = L::CIN * L::KK;
   float* tb = reinterpret_cast<float*>(smem);
   static_assert(L::COUT * PER_CO * 4 <= L::SMEM * 2, "slab tile fits");
-  if (wq == 0) {
+  if (wgw && wq == 0) {
 #pragma unroll
     for (int j = 0; j < L::NW; ++j) {
-      const int tap = 2 * (wc * L::NW + j) + (r16 >> 3), ci = r16 & 7;
+      const int tap = L::CIN == 8 ? 2 * (wc * L::NW + j) + (r16 >> 3) : wc * L::NW + j;
+      const int ci = L::CIN == 8 ? (r16 & 7) : r16;
       if (tap >= L::KK) continue;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) tb[(4 * g + i) * PER_CO + ci * L::KK + tap] = wacc[j][i];
+      for (int m = 0; m < L::MT; ++m)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          tb[(16 * m + 4 * g + i) * PER_CO + ci * L::KK + tap] = wacc[m * L::NW + j][i];
     }
   }
   __syncthreads();
@@ -550,16 +675,27 @@ __global__ __launch_bounds__(256, L::OCC) void lbwd_kernel(const bf16* __restric
 #ifndef LBWD_WGU
 #define LBWD_WGU 1
 #endif
-//          TH OCC PFD GB NCW RP BAL       WGU
-typedef Lb<8, 2, 3, 1, 4, 1, LBWD_BAL, LBWD_WGU> LbA2;
+//        CIN COUT H   W  TH OCC PFD GB NCW RP BAL       WGU       SP
+typedef Lb<8, 16, 56, 56, 8, 2, 3, 1, 4, 1, LBWD_BAL, LBWD_WGU> LbA2;   // audio conv2
+// audio conv3: 4-row tiles (7 per sample, continuation rows reused), double-buffered 72 KB, two
+// blocks per CU; waves 0-1 input gradient (7 groups of 16 pixels), waves 2-3 weight gradient
+// (4 padded rows x 13 column tiles x 2 row tiles each)
+#ifndef LBWD28_PFD
+#define LBWD28_PFD 3
+#endif
+#ifndef LBWD28_GB
+#define LBWD28_GB 1
+#endif
+typedef Lb<16, 32, 28, 28, 4, 2, LBWD28_PFD, LBWD28_GB, 2, 0, 0, 2, 1> LbA3;
 
+template <class L>
 int lb_occ_ap() {
   static int occ = 0;
   if (!occ) {
     // the least of the two apply variants, so one slab count serves both
     int o1 = 0, o2 = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o1, lbwd_kernel<LbA2, 1>, 256, 0) == hipSuccess &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&o2, lbwd_kernel<LbA2, 2>, 256, 0) == hipSuccess)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o1, lbwd_kernel<L, 1>, 256, 0) == hipSuccess &&
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&o2, lbwd_kernel<L, 2>, 256, 0) == hipSuccess)
       occ = std::min(o1, o2);
     if (occ <= 0)
       occ = 1;
@@ -578,20 +714,49 @@ int lb_cus() {
   return cus;
 }
 
+template <class L>
+bool lb_is(int Cin, int H, int W, int Cout, int K, int pad) {
+  return Cin == L::CIN && Cout == L::COUT && K == L::K && pad == L::PAD && H == L::H && W == L::W;
+}
+
+// the served shapes: the audio conv2 (56^2, 8 -> 16) and conv3 (28^2, 16 -> 32), 5x5 pad 2, bf16
 bool lb_serves(int dt, int N, int Cin, int H, int W, int Cout, int K, int pad) {
-  return dt == AVD_BF16 && !g_opts.generic_conv && N > 0 && Cin == LbA2::CIN && Cout == LbA2::COUT &&
-         K == LbA2::K && pad == LbA2::PAD && H == LbA2::H && W == LbA2::W;
+  return dt == AVD_BF16 && !g_opts.generic_conv && N > 0 &&
+         (lb_is<LbA2>(Cin, H, W, Cout, K, pad) || lb_is<LbA3>(Cin, H, W, Cout, K, pad));
+}
+
+template <class L>
+int lb_slabs(int N) {
+  return std::max(1, grid_cap(std::min(N * L::TPS, lb_cus() * lb_occ_ap<L>())));
 }
 
 }  // namespace
 
 int avd_cl_layer_bwd_slabs(int dt, int N, int Cin, int H, int W, int Cout, int K, int pad) {
   if (!lb_serves(dt, N, Cin, H, W, Cout, K, pad)) return 0;
-  const int ntiles = N * LbA2::TPS;
-  return std::max(1, grid_cap(std::min(ntiles, lb_cus() * lb_occ_ap())));
+  return lb_is<LbA3>(Cin, H, W, Cout, K, pad) ? lb_slabs<LbA3>(N) : lb_slabs<LbA2>(N);
 }
 
 namespace {
+template <class L>
+int lbwd_launch_as(const void* y, const void* x, const void* wk_d, void* dx, float* parts, int slabs,
+                   int N, bool ap, const ApplyArgs& aa, hipStream_t st) {
+  const int ntiles = N * L::TPS;
+  // the caller's slab count (the parts buffer it sized) is the grid: no re-derivation here
+  if (slabs < 1 || slabs > ntiles) return AVD_ERR_ARG;
+  if (ap && aa.codes)
+    lbwd_kernel<L, 2><<<slabs, 256, 0, st>>>((const bf16*)y, (const bf16*)x, (const bf16*)wk_d, (bf16*)dx,
+                                              parts, ntiles, aa);
+  else if (ap)
+    lbwd_kernel<L, 1><<<slabs, 256, 0, st>>>((const bf16*)y, (const bf16*)x, (const bf16*)wk_d, (bf16*)dx,
+                                              parts, ntiles, aa);
+  else
+    lbwd_kernel<L, 0><<<slabs, 256, 0, st>>>((const bf16*)y, (const bf16*)x, (const bf16*)wk_d, (bf16*)dx,
+                                              parts, ntiles, aa);
+  AVD_CHECK_LAUNCH();
+  return AVD_OK;
+}
+
 int lbwd_launch(const void* y, const void* gout, const float* scale, const float* shift,
                 const unsigned* codes, const float* coef, const void* dy, const void* x,
                 const void* wk_d, void* dx, float* parts, int slabs, int dt, int N, int B, int Cin,
@@ -604,25 +769,15 @@ int lbwd_launch(const void* y, const void* gout, const float* scale, const float
   const bool ap = y != nullptr;
   if (ap ? (!gout || !coef || (codes ? false : (!scale || !shift))) : !dy) return AVD_ERR_ARG;
   if (ap && (B <= 0 || N % B || N / B > APPLY_GMAX)) return AVD_ERR_SHAPE;
-  const int ntiles = N * LbA2::TPS;
-  // the caller's slab count (the parts buffer it sized) is the grid: no re-derivation here
-  if (slabs < 1 || slabs > ntiles) return AVD_ERR_ARG;
   ApplyArgs aa{};
   aa.gout = gout; aa.scale = scale; aa.shift = shift; aa.coef = coef;
   aa.B = ap ? B : N; aa.G = ap ? N / B : 1;
   aa.codes = codes;
   hipStream_t st = avd_stream(stream);
-  if (ap && codes)
-    lbwd_kernel<LbA2, 2><<<slabs, 256, 0, st>>>((const bf16*)y, (const bf16*)x, (const bf16*)wk_d, (bf16*)dx,
-                                                 parts, ntiles, aa);
-  else if (ap)
-    lbwd_kernel<LbA2, 1><<<slabs, 256, 0, st>>>((const bf16*)y, (const bf16*)x, (const bf16*)wk_d, (bf16*)dx,
-                                                 parts, ntiles, aa);
-  else
-    lbwd_kernel<LbA2, 0><<<slabs, 256, 0, st>>>((const bf16*)dy, (const bf16*)x, (const bf16*)wk_d, (bf16*)dx,
-                                                 parts, ntiles, aa);
-  AVD_CHECK_LAUNCH();
-  return AVD_OK;
+  const void* src = ap ? y : dy;
+  if (lb_is<LbA3>(Cin, H, W, Cout, K, pad))
+    return lbwd_launch_as<LbA3>(src, x, wk_d, dx, parts, slabs, N, ap, aa, st);
+  return lbwd_launch_as<LbA2>(src, x, wk_d, dx, parts, slabs, N, ap, aa, st);
 }
 }  // namespace
 
