@@ -7,7 +7,9 @@ serve (> 0) matters.
 The decision is spread over four predicates in the forward (_recompute_ok / _gram_ok /
 _pixel_major / _codes_ok) and inferred again by the backward from its ctx; ``first_layer_route``
 below reads them the way forward and backward do.  The table is what a single route function
-replacing them has to reproduce."""
+replacing them has to reproduce (tests/test_gpu_first_layer_launches.py ties its fields to the
+launches).  The "single5_*" rows are one-layer stacks: no route, yet their stored-y first layer
+is the one place where forward's recompute apply (RC_APPLY) runs in training."""
 import itertools
 
 import pytest
@@ -27,6 +29,9 @@ STACKS = {
     "rc64": S.cnn3_stack("s", [(1, 64, 3, 1), (64, 128, 3, 1)], 28),
     "single": S.cnn3_stack("s", [(1, 32, 3, 1)], 28),
     "w30": S.cnn3_stack("s", [(1, 32, 3, 1), (32, 64, 3, 1)], 30),        # W % 4 == 2
+    # one layer, flatten tail: the first layer is also the last and stores y
+    "single5_audio": S.central_stack("s", [(1, 8, 5, 2)], 112),
+    "single5_image": S.central_stack("s", [(1, 32, 5, 2)], 28),
 }
 SHIPPED = ("central_image", "central_audio", "cnn3_image", "cnn3_audio")
 SWITCHES = {"default": {}, "CODES=False": {"CODES": False}, "CODES3=False": {"CODES3": False},
@@ -65,6 +70,10 @@ ROWS = [
     ("single", ANY, False, ALL, None),
     ("w30", ANY, True, ALL, None),
     ("w30", ANY, False, ALL, None),
+    ("single5_audio", ANY, True, ALL, None),
+    ("single5_audio", ANY, False, ALL, None),
+    ("single5_image", ANY, True, ALL, None),
+    ("single5_image", ANY, False, ALL, None),
 ]
 CASES = [(stack, nb, nd, sw, exp) for stack, nbs, nd, sws, exp in ROWS for nb in nbs for sw in sws]
 
@@ -128,6 +137,36 @@ def test_recompute_passes_serve_a_shape_together():
         assert all(rows) or not any(rows), (dt, co, k, pad, H, N, B, rows)
         served += rows[0]
     assert served > 0
+
+
+def test_recompute_passes_refuse_other_kernel_sizes():
+    """The library serves 3x3 and 5x5 first layers only: no recompute pass has rows for any other
+    kernel size, so "the statistics pass has rows" already implies k is 3 or 5."""
+    for dt, ci, co, (k, pad), H, (N, B) in itertools.product(
+            (torch.bfloat16, torch.float32), (1, 2), (8, 16, 32, 64, 128),
+            ((1, 0), (2, 1), (4, 2), (7, 3), (9, 4)), range(4, 132, 2), ANY + ((7168, 1024),)):
+        rows = [ops.cl_c1_recompute_rows(p, dt, N, B, ci, H, H, co, k, pad) for p in range(5)]
+        assert not any(rows), (dt, ci, co, k, pad, H, N, B, rows)
+
+
+@pytest.mark.parametrize("stack", ["single5_audio", "single5_image"])
+def test_single_layer_stored_y_takes_the_recompute_apply(stack):
+    """A one-layer stack has no route (its first layer is also its last and stores y), but in
+    bf16 in front of a flatten tail (hwc: tail mode 0) ConvBranch.forward still pools it through
+    cl_c1_recompute(C1_APPLY) rather than cl_bn_relu_pool: the stored-y branch's condition
+    (first layer, mode 0, RC_APPLY, bf16, pass 1 has rows) holds.  It fails in f32 and in front
+    of the f32 (c, h, w) flatten (mode 2)."""
+    ci, co, k, pad = STACKS[stack].convs[0]
+    H = STACKS[stack].hw
+
+    def takes_apply(cb, N, B):
+        return (cb._tail_mode() == 0 and cb.RC_APPLY and cb.act == torch.bfloat16 and
+                ops.cl_c1_recompute_rows(ops.C1_APPLY, cb.act, N, B, ci, H, H, co, k, pad) > 0)
+
+    for N, B in ANY:
+        assert takes_apply(ConvBranch(STACKS[stack], torch.bfloat16, hwc=True), N, B)
+        assert not takes_apply(ConvBranch(STACKS[stack], torch.float32, hwc=True), N, B)
+        assert not takes_apply(ConvBranch(STACKS[stack], torch.bfloat16), N, B)
 
 
 def test_shipped_first_layers_are_the_table():
