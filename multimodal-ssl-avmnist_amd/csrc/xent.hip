@@ -24,6 +24,15 @@
 // The S^T / S accumulator layout (lane = one row / one column, 8 entries) is the B operand of
 // the second MFMA as is: its 8 k values {4g..4g+3, 16+4g..16+4g+3} are matched by reading the
 // A operand (K^T / Q^T) with ds_read_b64_tr_b16 in the same order (wgrad_ws.hip's kpix).
+//
+// Precision (restated in float64 by tests/xent_ref.py, which must be kept in step): Q and K are
+// rounded to bf16 for both products, P is rounded to bf16 before P K and P^T Q; S, the online
+// max / sum, lse and L are f32; the target score and the subtracted k_t / q_i terms come from the
+// unrounded f32 vectors.  Hence loss_i = lse(bf16-operand scores) - (f32 target score) can come
+// out slightly NEGATIVE on a converged row (lse ~ the target's score: what is left is the
+// rounding of one scaled score), where the true CE cannot: loss_i >= -(inv_t 2^-8 1.01 + 1e-5)
+// for unit rows is what the tests hold it to (tests/test_gpu_xent_edges.py).  The f32 target
+// score is kept because it is the more accurate on unconverged rows, which carry the logged loss.
 #include <algorithm>
 #include <math.h>
 
@@ -390,10 +399,11 @@ int avd_xent_fused(const float* q, const float* k, int R, int C, int P, int Bh, 
   if (!q || !k || !loss || !dq || !dk || !ws) return AVD_ERR_ARG;
   const int need = avd_xent_fused_ws(R, C, P);
   if (need < 0 || Bh <= 0 || Bh > R || R > 2 * Bh) return AVD_ERR_SHAPE;
-  if (ws_elems < need) return AVD_ERR_ARG;
-  // every target column must exist (the reference's labels index S's columns)
+  // every target column must exist (the reference's labels index S's columns); tgt1 only
+  // where there is a second half
   const int r1 = R > Bh ? R - Bh : 0;
   if (tgt0 < 0 || tgt0 + Bh > C || (r1 && (tgt1 < 0 || tgt1 + r1 > C))) return AVD_ERR_SHAPE;
+  if (ws_elems < need) return AVD_ERR_ARG;   // after the shape checks: the last gate before the launches
   XArgs a{q, k, R, C, Bh, tgt0, tgt1, msk0, msk1, inv_t, gscale};
   const int sa = xsplit((R + 63) / 64), sb = xsplit((C + 63) / 64);
   float* pm = ws;

@@ -125,3 +125,35 @@ def test_small_reductions_and_fused_xent_workspace(lib):
     assert lib.avd_bn_eval_coef(d, d, d, None, 1e-5, 4, d, d, None) == ARG
     assert lib.avd_xent_fused_ws(256, 256, 64) == SHAPE
     assert lib.avd_xent_fused_ws(256, 256, 128) > 0
+
+
+def test_xent_fused_arguments(lib):
+    """avd_xent_fused's own checks, in their order: null pointers (ARG), shapes and target
+    ranges (SHAPE), then the workspace size (ARG) as the last gate before the launches.  No
+    call here passes that gate: every one that passes the shape checks is given a workspace one
+    element short, so ARG from such a call means 'accepted up to the workspace check'."""
+    R, C, P, Bh = 10, 24, 128, 5
+    need = lib.avd_xent_fused_ws(R, C, P)
+    assert need > 0
+
+    def xent(q=d, k=d, R=R, C=C, P=P, Bh=Bh, tgt=(5, 0), msk=(0, 5), loss=d, dq=d, dk=d, ws=d, short=1):
+        n = lib.avd_xent_fused_ws(R, C, P)
+        return lib.avd_xent_fused(q, k, R, C, P, Bh, tgt[0], tgt[1], msk[0], msk[1], 14.0, 0.1, loss,
+                                  dq, dk, ws, max(n, 0) - short, None)
+
+    for name in ("q", "k", "loss", "dq", "dk", "ws"):
+        assert xent(**{name: None}) == ARG, name
+    assert xent(P=64) == SHAPE
+    assert xent(R=0) == SHAPE and xent(C=0) == SHAPE
+    assert xent(Bh=0) == SHAPE and xent(Bh=11) == SHAPE         # Bh > R
+    assert xent(Bh=4) == SHAPE                                  # R > 2 Bh
+    assert xent(tgt=(-1, 0)) == SHAPE and xent(tgt=(20, 0)) == SHAPE        # tgt0 + Bh = 25 > C
+    assert xent(tgt=(5, -1)) == SHAPE and xent(tgt=(5, 20)) == SHAPE        # tgt1 + (R - Bh) > C
+    assert xent(R=9, tgt=(5, 21)) == SHAPE                      # ragged second half: 21 + 4 > C
+    # the largest targets that fit, a ragged second half, no masks: accepted
+    assert xent(tgt=(19, 19)) == ARG and xent(R=9, tgt=(19, 20)) == ARG and xent(msk=(-1, -1)) == ARG
+    # one half (R = Bh): tgt1 is not read, tgt0 still is
+    assert xent(Bh=10, tgt=(5, -1)) == ARG and xent(Bh=10, tgt=(5, 1000)) == ARG
+    assert xent(Bh=10, tgt=(15, 0)) == SHAPE and xent(Bh=10, tgt=(14, 0)) == ARG
+    # the workspace: one short is refused, and only that (the shape checks come first)
+    assert xent(short=1) == ARG and xent(tgt=(-1, 0), short=1) == SHAPE and xent(ws=None, P=64) == ARG
