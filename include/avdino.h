@@ -357,6 +357,96 @@ int avd_lstm_bwd(const float* dout, const float* whh_f, const float* whh_r, cons
  * even), else AVD_ERR_DTYPE -- the NHWC bf16 token map into the f32 GEMMs and its gradient back. */
 int avd_cast(const void* src, int src_dt, void* dst, int dst_dt, long long n, void* stream);
 
+/* ------------------------------------------------------------------ ViT encoders (vit.hip)
+ * AudioViTEncoder / ViTEncoder (models/dino_vit.py:27-63, 65-177) over
+ * nn.TransformerEncoderLayer(post-norm, gelu, batch_first).  Every Linear is avd_gemm /
+ * avd_linear_bwd; the entry points below are what lies between them.  The dropout sites take
+ * (p, seed, seed_off): keep scale 0 or 1/(1-p) from the counter hash of (seed + *seed_off, key)
+ * (seed_off: device memory, nullable; the step state of avd_step_begin), regenerated by the
+ * backward; p = 0 evaluates no hash.  p outside [0, 1) is AVD_ERR_ARG. */
+
+/* Multi-head self-attention of N independent sequences of T tokens, `heads` heads of dh features:
+ *   ctx[n, i, h*dh + c] = sum_j D[n,h,i,j] V[n, j, h*dh + c],
+ *   D = dropout(softmax_j(scale Q[n,i,h] . K[n,j,h])),  dropout key ((n*heads + h)*T + i)*T + j,
+ * applied to the normalised probabilities.  q / k / v / ctx are f32 row matrices [N*T, heads*dh]
+ * given by pointer and leading dimension, so Q, K, V can be the column slices 0, E, 2E of one
+ * [N*T, 3E] in-projection buffer.  No residual is added.  lse (nullable: teacher and eval
+ * passes) [N][heads][T] = the row log-sum-exp of the scaled scores, for avd_mhsa_bwd; with lse
+ * NULL the rest is bit-identical.  One workgroup owns 16 query rows of one (sequence, head) and
+ * all T keys; the score tile lives in LDS, never in HBM; keys past T are excluded from max and
+ * sum, rows past T are never written.
+ * dt = AVD_F32: exact f32 fma chains (the parity yardstick).  dt = AVD_BF16: Q, K, V and the
+ * dropped-out probabilities are rounded to bf16 (the operands of the two products), f32
+ * accumulation -- on the VALU in this version, not yet on the MFMA.
+ * dh in {32, 64, 128}, heads >= 1, 1 <= T <= 256, 1 <= N <= 65535, else AVD_ERR_SHAPE; pointers
+ * 16-byte aligned, leading dimensions >= heads*dh and multiples of 4 floats, else AVD_ERR_ARG;
+ * dt other than the two: AVD_ERR_DTYPE. */
+int avd_mhsa_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v,
+                 long long ldv, float* ctx, long long ldo, float* lse, int N, int heads, int T, int dh,
+                 int dt, float scale, float p, unsigned long long seed,
+                 const unsigned long long* seed_off, void* stream);
+/* Its backward: with P recomputed from lse and the mask M regenerated,
+ *   dV = (P o M)^T dO,  dP = (dO V^T) o M,  delta = rowsum(P o dP),  dS = P o (dP - delta),
+ *   dQ = scale dS K,  dK = scale dS^T Q.
+ * A row pass (16 query rows per workgroup: dQ, and into ws per row the renormalisation
+ * 1 / sum_j exp(S - lse) and delta) and a column pass (16 key rows: dK, dV); no T x T array in
+ * HBM, no atomics, every sum in a fixed order: two runs are bit-identical.  P is renormalised by
+ * its own row sum (lse is an f32: at |lse| ~ 100 exp(S - lse) is off by 7e-6) and
+ * delta = sum_j P dP / sum_j P is formed in double and passed as a (hi, lo) pair of floats: in a
+ * row whose softmax is nearly one-hot dP_top - delta is (1 - P_top) |dP|, which an f32 delta
+ * (good to 6e-8 |dP|) would swamp.
+ * dt = AVD_BF16 rounds Q, K, V, dO, P o M and dS to bf16.  ws: avd_mhsa_bwd_ws(...) floats
+ * (-1: unsupported shape).  Shapes, alignment and codes as avd_mhsa_fwd. */
+long long avd_mhsa_bwd_ws(int N, int heads, int T, int dh);
+int avd_mhsa_bwd(const float* dout, long long lddo, const float* q, long long ldq, const float* k,
+                 long long ldk, const float* v, long long ldv, const float* lse, float* dq,
+                 long long lddq, float* dk, long long lddk, float* dv, long long lddv, float* ws,
+                 long long ws_elems, int N, int heads, int T, int dh, int dt, float scale, float p,
+                 unsigned long long seed, const unsigned long long* seed_off, void* stream);
+
+/* y[r] = LayerNorm(x[r] + dropout(res[r])) * gamma + beta over rows of E features (biased
+ * variance, eps inside the square root: nn.LayerNorm); res nullable = plain LayerNorm (p is then
+ * ignored).  x / res / y rows are ldx / ldr / ldy floats apart (the final norm runs on the N
+ * cls rows with ldx = T*E).  The dropout key is row*E + c.  Nullable outputs for the backward:
+ * z [rows][E] the pre-norm sum, mean [rows], rstd [rows].
+ * E a multiple of 32, 32..512, rows >= 1, else AVD_ERR_SHAPE; NULL / ld < E: AVD_ERR_ARG. */
+int avd_ln_fwd(const float* x, long long ldx, const float* res, long long ldr, const float* gamma,
+               const float* beta, float* y, long long ldy, float* z, float* mean, float* rstd,
+               int rows, int E, float eps, float p, unsigned long long seed,
+               const unsigned long long* seed_off, void* stream);
+/* Backward: with xhat = (z - mean) rstd and g = dy gamma,
+ *   dx = rstd (g - mean_c(g) - xhat mean_c(g xhat))      the skip path,
+ *   dr = mask o dx                                       the branch (nullable; p ignored if NULL),
+ *   dgamma = sum_r dy xhat,  dbeta = sum_r dy            two-stage: per-workgroup column partials
+ * in ws (avd_ln_bwd_ws floats; -1: unsupported shape), then summed in workgroup order -- no
+ * atomics, bit-reproducible.  dy / dx / dr rows are lddy / lddx / lddr floats apart. */
+long long avd_ln_bwd_ws(int rows, int E);
+int avd_ln_bwd(const float* dy, long long lddy, const float* z, const float* mean, const float* rstd,
+               const float* gamma, float* dx, long long lddx, float* dr, long long lddr, float* dgamma,
+               float* dbeta, float* ws, long long ws_elems, int rows, int E, float p,
+               unsigned long long seed, const unsigned long long* seed_off, void* stream);
+
+/* out = dropout(gelu(x)) (erf form) over [rows, C] f32, dropout key = the element index; and the
+ * backward on the pre-activation: dx = dout o mask o gelu'(x).  (avd_act_fwd's act 1 is GELU
+ * behind a BatchNorm affine; this one has none.  The Linear bias stays in avd_gemm.) */
+int avd_gelu_fwd(const float* x, float* out, long long rows, int C, float p, unsigned long long seed,
+                 const unsigned long long* seed_off, void* stream);
+int avd_gelu_bwd(const float* x, const float* dout, float* dx, long long rows, int C, float p,
+                 unsigned long long seed, const unsigned long long* seed_off, void* stream);
+
+/* Patch rows of a staged one-channel NHWC map x [N][H][W] (dt: AVD_F32 or AVD_BF16):
+ *   out[(n*(H/P) + gy)*(W/P) + gx][ph*P + pw] = x[n][gy*P + ph][gx*P + pw]     (f32, exact),
+ * the (ph, pw) order of the patch Conv2d's weight [E][1][P][P], so the embedding is one GEMM with
+ * K = P*P.  H, W multiples of P, else AVD_ERR_SHAPE. */
+int avd_vit_patchify(const void* x, int dt, float* out, int N, int H, int W, int P, void* stream);
+/* tok [N][T][E]: row 0 = cls + pos[0], row 1+t = pe[n*(T-1) + t] + pos[1+t]  (pe [N*(T-1)][E] the
+ * patch embeddings, cls [E], pos [T][E]).  Backward: dpe[n*(T-1) + t] = dtok[n][1+t] (the patch
+ * rows compacted for avd_linear_bwd); dpos = avd_sum_rows over the [N, T*E] view of dtok and
+ * dcls = dpos row 0.  T >= 2. */
+int avd_vit_tokens_fwd(const float* pe, const float* cls, const float* pos, float* tok, int N, int T,
+                       int E, void* stream);
+int avd_vit_tokens_bwd(const float* dtok, float* dpe, int N, int T, int E, void* stream);
+
 /* Test hook: fill the LDS of every CU with NaN bit patterns (0x7fc07fc0), so a kernel that reads
  * LDS it never wrote sees NaN instead of a benign leftover (tools/lds_poison.py). */
 int avd_lds_poison(void* stream);

@@ -86,6 +86,17 @@ PROTOS = {
     "avd_lstm_fwd": [P, P, P, P, P, I, I, I, I, I, P],
     "avd_lstm_bwd": [P, P, P, P, P, I, I, I, I, P],
     "avd_cast": [P, I, P, I, L, P],
+    "avd_mhsa_fwd": [P, L, P, L, P, L, P, L, P, I, I, I, I, I, F, F, U64, P, P],
+    "avd_mhsa_bwd_ws": [I, I, I, I],
+    "avd_mhsa_bwd": [P, L, P, L, P, L, P, L, P, P, L, P, L, P, L, P, L, I, I, I, I, I, F, F, U64, P, P],
+    "avd_ln_fwd": [P, L, P, L, P, P, P, L, P, P, P, I, I, F, F, U64, P, P],
+    "avd_ln_bwd_ws": [I, I],
+    "avd_ln_bwd": [P, L, P, P, P, P, P, L, P, L, P, P, P, L, I, I, F, U64, P, P],
+    "avd_gelu_fwd": [P, P, L, I, F, U64, P, P],
+    "avd_gelu_bwd": [P, P, P, L, I, F, U64, P, P],
+    "avd_vit_patchify": [P, I, P, I, I, I, I, P],
+    "avd_vit_tokens_fwd": [P, P, P, P, I, I, I, P],
+    "avd_vit_tokens_bwd": [P, P, I, I, I, P],
     "avd_cl_layer_bwd_slabs": [I, I, I, I, I, I, I, I],
     "avd_cl_layer_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     "avd_cl_layer_bwd_codes": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
@@ -172,6 +183,8 @@ def _load():
         fn.restype = ctypes.c_int
     lib.avd_gemm_ws_elems.restype = ctypes.c_longlong
     lib.avd_linear_hwc_ws_elems.restype = ctypes.c_longlong
+    lib.avd_mhsa_bwd_ws.restype = ctypes.c_longlong
+    lib.avd_ln_bwd_ws.restype = ctypes.c_longlong
     lib.avd_mx_weight_bytes.restype = ctypes.c_longlong
     lib.avd_mx_scale_bytes.restype = ctypes.c_longlong
     lib.avd_last_error.argtypes = []

@@ -25,7 +25,8 @@ import torch
 from . import contrastive, ops
 from .capture import GraphedStep, host_point, new_event  # noqa: F401  (GraphedStep re-exported)
 from .spec import (HEAD_NAMES, LSTM_PROJ, MIX_KIND, MULTI_ENCODERS, PROJ_HIDDEN, UNI_ALIASES,
-                   UNI_ENCODERS, XATTN_NAMES, lstm_hidden)
+                   UNI_ENCODERS, VIT_ENCODERS, XATTN_NAMES, lstm_hidden)
+from .vit import ViTTower
 
 F32 = torch.float32
 # early gradient buckets at a host point inside the step (False: one all-reduce after the step)
@@ -767,7 +768,10 @@ class ProjHead:
 class Hyper:
     def __init__(self, lr=1e-4, weight_decay=1e-6, momentum=0.996, center_momentum=0.9,
                  student_temperature=0.1, teacher_temperature=0.04, dropout=0.3,
-                 fusion_dropout=0.3, alpha=1.0, betas=(0.9, 0.999), eps=1e-8):
+                 fusion_dropout=0.3, alpha=1.0, betas=(0.9, 0.999), eps=1e-8, vit_dropout=0.1):
+        """vit_dropout: the four dropout sites of every transformer layer of a ViT encoder
+        (TransformerEncoder's default 0.1, models/dino_vit.py:44); the other kinds have none."""
+        self.vit_dropout = vit_dropout
         self.lr, self.wd = lr, weight_decay
         self.momentum, self.center_momentum = momentum, center_momentum
         self.tau_s, self.tau_t = student_temperature, teacher_temperature
@@ -1762,17 +1766,29 @@ class UniEncoder:
     SpectrogramEncoderLSTM (525-530, LSTMAudioEncoder 117-156; ``out_dim`` required): the pooled
     14 x 14 x 128 map as 196 token rows -> Linear(128,64) + ReLU per token -> bidirectional
     LSTM(64, D/2) -> mean over the tokens.  The input projections and every weight gradient are
-    GEMMs; the recurrence is avd_lstm_fwd / avd_lstm_bwd."""
+    GEMMs; the recurrence is avd_lstm_fwd / avd_lstm_bwd.
+    SpectrogramEncoderViT (532-546; a spec.VIT_ENCODERS kind): no conv stack -- the staged map goes
+    through a ViTTower (avdino/vit.py), then Linear(512, D) on its cls rows.
+    ``drop`` = (p, base seed, seed_off, role) switches the tower's dropout on (vit.py; the other
+    kinds have none and ignore it)."""
 
     def __init__(self, kind, prefix, act_dtype, gemm_mode, out_dim=None):
         kind = UNI_ALIASES.get(kind, kind)
+        self.vit = kind in VIT_ENCODERS
+        self.gm = gemm_mode
+        if self.vit:
+            modality, tprefix, dims, lins, _sd = VIT_ENCODERS[kind]
+            self.modality, self.lstm, self.branch = modality, False, None
+            self.hw = dims["hw"]
+            self.tower = ViTTower(f"{prefix}.{tprefix}", act_dtype=act_dtype, gemm_mode=gemm_mode, **dims)
+            self.lins = [f"{prefix}.{k}" for k in lins]
+            return
         modality, stack, lins, _sd = UNI_ENCODERS[kind]
         self.modality = modality
         self.hw = 28 if modality == "image" else 112
         self.lstm = kind == "spectrogram_lstm"
         self.branch = ConvBranch(stack(prefix), act_dtype, nhwc_tail=self.lstm)
         self.lins = [f"{prefix}.{k}" for k in lins]
-        self.gm = gemm_mode
         if self.lstm:
             self.H = lstm_hidden(out_dim)
             self.lk = f"{prefix}.encoder.lstm."
@@ -1817,8 +1833,12 @@ class UniEncoder:
         ops.cast(dtok, dmap, R * C)
         return dmap
 
-    def forward(self, ws, store, tag, x, N, G, need_dgrad):
-        feat, ctx = self.branch.forward(ws, store, tag, x, N, G, True, need_dgrad)
+    def forward(self, ws, store, tag, x, N, G, need_dgrad, drop=None):
+        if self.vit:
+            feat, ctx = self.tower.forward(ws, store, tag, x, N, need_dgrad, drop)
+            ctx = dict(N=N, tower=ctx)
+        else:
+            feat, ctx = self.branch.forward(ws, store, tag, x, N, G, True, need_dgrad)
         if self.lstm:
             out, saved = self._lstm_forward(ws, store, tag, feat, N, need_dgrad)
             return out, (ctx, saved)
@@ -1833,7 +1853,10 @@ class UniEncoder:
         return h.view(N, -1), (ctx, acts)
 
     def forward_eval(self, ws, store, tag, x, N):
-        h = self.branch.forward_eval(ws, store, tag, x, N)
+        if self.vit:
+            h = self.tower.forward_eval(ws, store, tag, x, N)
+        else:
+            h = self.branch.forward_eval(ws, store, tag, x, N)
         if self.lstm:
             return self._lstm_forward(ws, store, tag, h, N, False)[0]
         for i, k in enumerate(self.lins):
@@ -1857,6 +1880,9 @@ class UniEncoder:
             ops.linear_bwd(g, acts[i], w, store.grad_of(k + ".weight"), store.grad_of(k + ".bias"),
                            dx, N, mode=self.gm)
             g = dx
+        if self.vit:
+            self.tower.backward(ws, store, bctx["tower"], g)
+            return
         self.branch.backward(ws, store, bctx, g)
 
 
@@ -1914,6 +1940,28 @@ class UniModalEngine:
     def forward(self, batch, training=True):
         return self._forward_staged(self.stage(batch), training)
 
+    def activation_bytes(self, Ns, Nt, training=True):
+        """Workspace bytes a ViT encoder's towers need for Ns student and Nt teacher sequences
+        (vit.py activation_elems; recomputation is not implemented, every layer's activations are
+        kept for the backward)."""
+        return 4 * (self.enc.tower.activation_elems(Ns, training) + self.t_enc.tower.activation_elems(Nt, False))
+
+    def _check_memory(self, Ns, Nt, training):
+        """Raise before the first allocation of a shape whose activations cannot fit the device."""
+        key = (Ns, Nt, training)
+        if getattr(self, "_mem_ok", None) == key or self.store.device.type != "cuda":
+            return
+        need = self.activation_bytes(Ns, Nt, training) - self.ws.nbytes()
+        free, _total = torch.cuda.mem_get_info(self.store.device)
+        cached = torch.cuda.memory_reserved(self.store.device) - torch.cuda.memory_allocated(self.store.device)
+        if need > free + cached:
+            raise MemoryError(
+                f"{self.kind}: {Ns} student + {Nt} teacher sequences need "
+                f"{self.activation_bytes(Ns, Nt, training) / 2 ** 30:.1f} GiB of activations (every transformer "
+                f"layer's are kept for the backward; DESIGN 3.11), the device has "
+                f"{(free + cached) / 2 ** 30:.1f} GiB free: use a smaller batch")
+        self._mem_ok = key
+
     def _forward_staged(self, staged, training=True):
         hp, ws, st, D, P = self.hp, self.ws, self.store, self.D, self.P
         x, B, G, L = staged
@@ -1922,8 +1970,17 @@ class UniModalEngine:
         if training:
             self.sstate.begin()
         base = (self.seed * 1000003) & SEED_MASK
-        emb, sctx = self.enc.forward(ws, st, "s", x, V * B, V, need_dgrad=training)
-        temb, _ = self.t_enc.forward(ws, st, "t", x[:G * B * HW], G * B, G, need_dgrad=False)
+        # a ViT encoder's dropout: student role 0, teacher role 1 (a train-mode module in the
+        # reference, so it drops too, with masks of its own); an eval pass draws nothing
+        sdrop = tdrop = None
+        if self.enc.vit:
+            self._check_memory(V * B, G * B, training)
+            vp = getattr(hp, "vit_dropout", 0.0)
+            if training and vp > 0:
+                sdrop = (vp, base, self.sstate.seed_off, 0)
+                tdrop = (vp, base, self.sstate.seed_off, 1)
+        emb, sctx = self.enc.forward(ws, st, "s", x, V * B, V, need_dgrad=training, drop=sdrop)
+        temb, _ = self.t_enc.forward(ws, st, "t", x[:G * B * HW], G * B, G, need_dgrad=False, drop=tdrop)
         s_proj = ws.get("s_proj", V * B * P)
         spc = self.sproj.forward(ws, st, "sp", emb, V * B, s_proj, hp.dropout, base + 3,
                                  seed_off=self.sstate.seed_off)

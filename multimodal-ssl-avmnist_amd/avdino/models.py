@@ -177,12 +177,21 @@ class SpectrogramEncoderLSTM(SpectrogramEncoder):
         super().__init__(output_dim)
 
 
+class SpectrogramEncoderViT(SpectrogramEncoder):
+    """Sequential(AudioViTEncoder(112, patch 8, embed_dim 512, depth 4, heads 4), Linear(512,
+    output_dim)) (models/dino.py:532-546; models/dino_vit.py:122-177): 196 patch tokens + cls,
+    four post-norm transformer layers, the final LayerNorm's cls row.  Descriptor: the tower is
+    avdino/vit.py ViTTower on csrc/vit.hip."""
+    kind = "spectrogram_vit"
+
+
 MODEL_MAP = {"multi_simple": SimpleMultiModalEncoder, "multi_simple_gated": GatedMultiModalEncoder,
              "multi_cross_attention": CrossAttentionMultiModalEncoder,
              "multi_central": CentralMultiModalEncoder}
 UNIMODAL_MODEL_MAP = {"image_simple": ImageEncoder, "spectrogram_simple": SpectrogramEncoder,
                       "spectrogram_central": SpectrogramEncoderCentral,
-                      "spectrogram_lstm": SpectrogramEncoderLSTM}
+                      "spectrogram_lstm": SpectrogramEncoderLSTM,
+                      "spectrogram_vit": SpectrogramEncoderViT}
 
 
 def _device(device):
@@ -963,7 +972,7 @@ class UniModalDINO(_ArenaModule):
         if getattr(enc, "kind", None) is None:
             raise NotImplementedError(
                 f"{encoder_class.__name__}: the MI355X engine runs ImageEncoder, SpectrogramEncoder, "
-                f"SpectrogramEncoderCentral and SpectrogramEncoderLSTM")
+                f"SpectrogramEncoderCentral, SpectrogramEncoderLSTM and SpectrogramEncoderViT")
         self.student_spec = enc
         self.projection_dim, self.output_dim = projection_dim, output_dim
         self.momentum, self.center_momentum, self.dropout = momentum, center_momentum, dropout

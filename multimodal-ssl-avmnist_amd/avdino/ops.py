@@ -1232,6 +1232,157 @@ def cast(src, dst, n):
     call("avd_cast", p(src), dtcode(src), p(dst), dtcode(dst), n, stream())
 
 
+# ---------------------------------------------------------------- ViT encoders (vit.hip)
+MHSA_HEAD_DIMS = (32, 64, 128)     # features per head the attention kernels serve
+MHSA_TMAX = 256                    # tokens per sequence
+LN_EMAX = 512
+
+
+def _mmat(m, rows, E, what):
+    """A strided attention operand (tensor, element offset, ld): rows at off + r ld.  Checks that
+    everything the kernel may touch lies inside the tensor; returns (address, ld)."""
+    t, off, ld = m
+    _need(t.dtype == torch.float32 and t.is_contiguous(), f"mhsa {what}: contiguous f32")
+    _need(ld >= E and ld % 4 == 0 and off % 4 == 0 and off >= 0,
+          f"mhsa {what}: ld >= heads*dh, ld / offset multiples of 4")
+    _need(off + (rows - 1) * ld + E <= t.numel(), f"mhsa {what} bounds")
+    return t.data_ptr() + 4 * off, ld
+
+
+def _mdims(N, heads, T, dh, drop_p):
+    _need(dh in MHSA_HEAD_DIMS, f"mhsa: head dim must be one of {MHSA_HEAD_DIMS} (got {dh})")
+    _need(heads >= 1 and 1 <= T <= MHSA_TMAX and 1 <= N <= 65535,
+          f"mhsa: heads >= 1, 1 <= T <= {MHSA_TMAX}, 1 <= N <= 65535 (got {heads}, {T}, {N})")
+    _need(0.0 <= drop_p < 1.0, "mhsa: dropout p in [0, 1)")
+
+
+def _soff(seed_off):
+    _need(seed_off is None or (seed_off.dtype == torch.int64 and seed_off.numel() >= 1) or
+          seed_off.dtype == torch.uint64, "seed_off: a device 64-bit integer")
+    return p(seed_off)
+
+
+def mhsa_fwd(q, k, v, ctx, lse, N, heads, T, dh, scale, bf16, drop_p=0.0, seed=0, seed_off=None):
+    """ctx = dropout(softmax(scale Q K^T)) V per (sequence, head) (avd_mhsa_fwd); operands are
+    (tensor, element offset, ld); lse [N*heads*T] or None."""
+    _mdims(N, heads, T, dh, drop_p)
+    E, R = heads * dh, N * T
+    a = [_mmat(m, R, E, n) for m, n in ((q, "q"), (k, "k"), (v, "v"), (ctx, "ctx"))]
+    _need(lse is None or (lse.dtype == torch.float32 and lse.is_contiguous()
+                          and lse.numel() >= N * heads * T), "mhsa lse size")
+    _timed(f"mhsa_fwd[{N}x{heads}x{T}x{dh} bf{int(bool(bf16))}]", 4 * 4 * R * E, 4 * N * heads * T * T * dh,
+           lambda: call("avd_mhsa_fwd", *[y for m in a for y in m], p(lse), N, heads, T, dh,
+                        BF16 if bf16 else F32, scale, drop_p, seed, _soff(seed_off), stream()))
+
+
+def mhsa_bwd_ws(N, heads, T, dh):
+    _mdims(N, heads, T, dh, 0.0)
+    return lib.avd_mhsa_bwd_ws(N, heads, T, dh)
+
+
+def mhsa_bwd(dout, q, k, v, lse, dq, dk, dv, ws, N, heads, T, dh, scale, bf16, drop_p=0.0, seed=0,
+             seed_off=None):
+    """dQ, dK, dV from dctx, Q, K, V and the forward's lse (avd_mhsa_bwd)."""
+    _mdims(N, heads, T, dh, drop_p)
+    E, R = heads * dh, N * T
+    a = [_mmat(m, R, E, n) for m, n in ((dout, "dout"), (q, "q"), (k, "k"), (v, "v"))]
+    g = [_mmat(m, R, E, n) for m, n in ((dq, "dq"), (dk, "dk"), (dv, "dv"))]
+    _need(lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= N * heads * T,
+          "mhsa lse size")
+    _need(ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= mhsa_bwd_ws(N, heads, T, dh),
+          "mhsa workspace")
+    _timed(f"mhsa_bwd[{N}x{heads}x{T}x{dh} bf{int(bool(bf16))}]", 4 * 7 * R * E, 10 * N * heads * T * T * dh,
+           lambda: call("avd_mhsa_bwd", *[y for m in a for y in m], p(lse), *[y for m in g for y in m],
+                        p(ws), ws.numel(), N, heads, T, dh, BF16 if bf16 else F32, scale, drop_p, seed,
+                        _soff(seed_off), stream()))
+
+
+def _lrows(t, off, ld, rows, E, what):
+    _need(t.dtype == torch.float32 and t.is_contiguous() and ld >= E and off >= 0
+          and off + (rows - 1) * ld + E <= t.numel(), f"layer norm {what} bounds")
+    return t.data_ptr() + 4 * off
+
+
+def _ldims(rows, E):
+    _need(rows >= 1 and 32 <= E <= LN_EMAX and E % 32 == 0,
+          f"layer norm: E a multiple of 32 up to {LN_EMAX}, rows >= 1 (got {E}, {rows})")
+
+
+def ln_fwd(x, res, gamma, beta, y, rows, E, z=None, mean=None, rstd=None, eps=1e-5, drop_p=0.0, seed=0,
+           seed_off=None, x_ld=None, x_off=0, res_ld=None, y_ld=None, y_off=0):
+    """y = LayerNorm(x + dropout(res)) (avd_ln_fwd); res None = plain LayerNorm; z / mean / rstd:
+    what ln_bwd reads, or None."""
+    _ldims(rows, E)
+    x_ld = E if x_ld is None else x_ld
+    res_ld = E if res_ld is None else res_ld
+    y_ld = E if y_ld is None else y_ld
+    _need(gamma.numel() >= E and beta.numel() >= E, "layer norm affine size")
+    _need(z is None or z.numel() >= rows * E, "layer norm z size")
+    _need((mean is None or mean.numel() >= rows) and (rstd is None or rstd.numel() >= rows),
+          "layer norm statistics size")
+    rp = None if res is None else _lrows(res, 0, res_ld, rows, E, "res")
+    call("avd_ln_fwd", _lrows(x, x_off, x_ld, rows, E, "x"), x_ld, rp, res_ld, p(gamma), p(beta),
+         _lrows(y, y_off, y_ld, rows, E, "y"), y_ld, p(z), p(mean), p(rstd), rows, E, eps, drop_p, seed,
+         _soff(seed_off), stream())
+
+
+def ln_bwd_ws(rows, E):
+    _ldims(rows, E)
+    return lib.avd_ln_bwd_ws(rows, E)
+
+
+def ln_bwd(dy, z, mean, rstd, gamma, dx, dr, dgamma, dbeta, ws, rows, E, drop_p=0.0, seed=0,
+           seed_off=None, dy_ld=None, dy_off=0, dx_ld=None, dx_off=0, dr_ld=None):
+    """dx (skip), dr = mask dx (branch, or None), dgamma, dbeta of ln_fwd (avd_ln_bwd)."""
+    _ldims(rows, E)
+    dy_ld = E if dy_ld is None else dy_ld
+    dx_ld = E if dx_ld is None else dx_ld
+    dr_ld = E if dr_ld is None else dr_ld
+    _need(z.numel() >= rows * E and mean.numel() >= rows and rstd.numel() >= rows
+          and gamma.numel() >= E and dgamma.numel() >= E and dbeta.numel() >= E, "layer norm sizes")
+    _need(ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= ln_bwd_ws(rows, E),
+          "layer norm workspace")
+    rp = None if dr is None else _lrows(dr, 0, dr_ld, rows, E, "dr")
+    call("avd_ln_bwd", _lrows(dy, dy_off, dy_ld, rows, E, "dy"), dy_ld, p(z), p(mean), p(rstd), p(gamma),
+         _lrows(dx, dx_off, dx_ld, rows, E, "dx"), dx_ld, rp, dr_ld, p(dgamma), p(dbeta), p(ws),
+         ws.numel(), rows, E, drop_p, seed, _soff(seed_off), stream())
+
+
+def gelu_fwd(x, out, rows, C, drop_p=0.0, seed=0, seed_off=None):
+    """out = dropout(gelu(x)) over [rows, C] (avd_gelu_fwd)."""
+    _need(rows >= 1 and C >= 1 and x.numel() >= rows * C and out.numel() >= rows * C
+          and x.dtype == torch.float32 and out.dtype == torch.float32, "gelu shapes")
+    call("avd_gelu_fwd", p(x), p(out), rows, C, drop_p, seed, _soff(seed_off), stream())
+
+
+def gelu_bwd(x, dout, dx, rows, C, drop_p=0.0, seed=0, seed_off=None):
+    _need(rows >= 1 and C >= 1 and min(x.numel(), dout.numel(), dx.numel()) >= rows * C
+          and x.dtype == dout.dtype == dx.dtype == torch.float32, "gelu shapes")
+    call("avd_gelu_bwd", p(x), p(dout), p(dx), rows, C, drop_p, seed, _soff(seed_off), stream())
+
+
+def vit_patchify(x, out, N, H, W, P):
+    """Staged map x [N, H, W] (f32 / bf16) -> f32 patch rows [N*(H/P)*(W/P), P*P] (avd_vit_patchify)."""
+    _need(N >= 1 and P >= 1 and H % P == 0 and W % P == 0, "patchify: H, W multiples of P")
+    _need(x.numel() >= N * H * W and out.numel() >= N * H * W and out.dtype == torch.float32,
+          "patchify bounds")
+    call("avd_vit_patchify", p(x), dtcode(x), p(out), N, H, W, P, stream())
+
+
+def vit_tokens_fwd(pe, cls, pos, tok, N, T, E):
+    _need(N >= 1 and T >= 2 and pe.numel() >= N * (T - 1) * E and cls.numel() >= E
+          and pos.numel() >= T * E and tok.numel() >= N * T * E, "vit tokens bounds")
+    for t in (pe, cls, pos, tok):
+        _need(t.dtype == torch.float32, "vit tokens are f32")
+    call("avd_vit_tokens_fwd", p(pe), p(cls), p(pos), p(tok), N, T, E, stream())
+
+
+def vit_tokens_bwd(dtok, dpe, N, T, E):
+    _need(N >= 1 and T >= 2 and dtok.numel() >= N * T * E and dpe.numel() >= N * (T - 1) * E
+          and dtok.dtype == dpe.dtype == torch.float32, "vit tokens bounds")
+    call("avd_vit_tokens_bwd", p(dtok), p(dpe), N, T, E, stream())
+
+
 def cosine_consistency(emb, V, B, D, alpha, loss_parts, demb):
     _need(emb.numel() >= V * B * D and (demb is None or demb.numel() >= V * B * D)
           and (loss_parts is None or loss_parts.numel() >= B), "cosine consistency shapes")

@@ -31,7 +31,7 @@ ALIGN = 16  # floats (64 B) per parameter slot
 
 
 def _is_param(kind):
-    return kind in ("w", "b", "bn_w", "bn_b", "gate", "lstm")
+    return kind in ("w", "b", "bn_w", "bn_b", "gate", "lstm", "ln_w", "ln_b", "tok", "attn_w", "attn_b")
 
 
 def _dead(key):
@@ -181,7 +181,12 @@ class ParamStore:
                 # hidden = a fourth of the leading (4H) dimension
                 b = 1.0 / math.sqrt(shape[0] // 4)
                 v = (torch.rand(shape, generator=g, dtype=torch.float64) * 2 - 1) * b
-            elif kind == "bn_w":
+            elif kind == "attn_w":
+                # nn.MultiheadAttention._reset_parameters: xavier_uniform_ on in_proj_weight
+                # [3E, E]; in_proj_bias and out_proj.bias ("attn_b") are zeros
+                b = math.sqrt(6.0 / (shape[0] + shape[1]))
+                v = (torch.rand(shape, generator=g, dtype=torch.float64) * 2 - 1) * b
+            elif kind in ("bn_w", "ln_w"):      # LayerNorm: ones / zeros; cls_token, pos_embed: zeros
                 v = torch.ones(shape, dtype=torch.float64)
             elif kind == "gate":
                 v = torch.full(shape, GATE_INIT, dtype=torch.float64)

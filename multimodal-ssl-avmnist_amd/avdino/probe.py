@@ -23,7 +23,7 @@ from . import ops
 from .capture import GraphedStep
 from .engine import F32, ConvBranch, MultiCentralEngine, StepState, UniEncoder, Workspace, mix_forward
 from .params import ParamStore
-from .spec import MIX_KIND, MULTI_ENCODERS, UNI_ALIASES, UNI_ENCODERS
+from .spec import MIX_KIND, MULTI_ENCODERS, UNI_ALIASES, uni_modality
 
 from collections import OrderedDict
 
@@ -185,7 +185,7 @@ class LinearProbe:
             self.enc = _MultiEncoder(self.kind, E, D, act_dtype, self.gm, fusion_dropout)
         else:
             self.enc = _UniEncoder(self.kind, act_dtype, self.gm, prefix, out_dim=D)
-            self.modality = UNI_ENCODERS[self.kind][0]
+            self.modality = uni_modality(self.kind)      # a conv-stack kind or a ViT one
         self.cls = ParamStore(classifier_sd(D), dev, seed=seed, has_teacher=False)
         if classifier_state is not None:
             self.cls.load_state_dict(classifier_state)

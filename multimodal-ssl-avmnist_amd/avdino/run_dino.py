@@ -194,12 +194,19 @@ def model_stats(model, G, L, B=1):
     spectrogram_lstm: after the conv stack, per sample and with T = 14 * 14 = 196 positions,
     H = output_dim / 2:  T * 128 * 64  (feature_proj per position)
                        + T * 2 * 4H * (64 + H)  (both directions: the input projection and the
-                                                 recurrent product of the four gates)."""
-    from .spec import LSTM_PROJ, MIX_KIND, MULTI_ENCODERS, UNI_ENCODERS, XATTN_NAMES
+                                                 recurrent product of the four gates).
+    spectrogram_vit: per sample, with Tp = (112 / 8)^2 = 196 patches, T = Tp + 1 tokens, E = 512,
+    F = 4E, 4 heads of dh = 128 and 4 layers:
+                         Tp * 64 * E                            (patch embedding)
+                       + 4 * [T * (3 E E + E E + 2 E F)         (in-proj, out-proj, the MLP)
+                              + 2 * heads * T * T * dh]         (Q K^T and P V)
+                       + E * output_dim                         (the Linear on the cls row)."""
+    from .spec import LSTM_PROJ, MIX_KIND, MULTI_ENCODERS, UNI_ENCODERS, VIT_ENCODERS, XATTN_NAMES
     m = model.model
     spec = m.store.spec
     params = sum(int(math.prod(shp)) for k, (shp, kind) in spec.items()
-                 if kind in ("w", "b", "bn_w", "bn_b", "gate", "lstm"))
+                 if kind in ("w", "b", "bn_w", "bn_b", "gate", "lstm", "ln_w", "ln_b", "tok", "attn_w",
+                             "attn_b"))
 
     def lin(key):
         shp = spec[key + ".weight"][0]
@@ -227,6 +234,15 @@ def model_stats(model, G, L, B=1):
             macs += branch_i + branch_a + sum(head(h) for h in heads)
     else:
         kind = m.student_spec.kind
+        if kind in VIT_ENCODERS:
+            _mod, _tp, d, lins, _sd = VIT_ENCODERS[kind]
+            E, Tp = d["embed_dim"], (d["hw"] // d["patch"]) ** 2
+            T, F, dh = Tp + 1, 4 * d["embed_dim"], d["embed_dim"] // d["heads"]
+            enc = (Tp * d["patch"] ** 2 * E
+                   + d["depth"] * (T * (3 * E * E + E * E + 2 * E * F) + 2 * d["heads"] * T * T * dh)
+                   + sum(lin(f"student.{k}") for k in lins))
+            macs = (G + L) * (enc + head("student_projection")) + G * (enc + head("teacher_projection"))
+            return macs / 1e9, params
         _mod, stack, lins, _sd = UNI_ENCODERS[kind]
         st = stack("student")
         if kind == "spectrogram_lstm":

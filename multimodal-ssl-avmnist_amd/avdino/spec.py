@@ -281,11 +281,71 @@ UNI_ENCODERS = {
 }
 UNI_ALIASES = {"image": "image_simple", "audio": "spectrogram_simple"}
 
+# SpectrogramEncoderViT (dino.py:532-546): Sequential(AudioViTEncoder(112, patch 8, embed 512,
+# depth 4, heads 4) (dino_vit.py:122-177), Linear(512, output_dim)).  The tower's parameters:
+# kinds "tok" (cls_token, pos_embed: zeros), "attn_w" (in_proj_weight: xavier-uniform), "attn_b"
+# (in_proj_bias, out_proj.bias: zeros), "ln_w" / "ln_b" (LayerNorm: ones / zeros); the patch
+# Conv2d and the Linears are "w" / "b".
+VIT_AUDIO = dict(hw=112, patch=8, embed_dim=512, depth=4, heads=4)
+VIT_MLP_RATIO = 4           # dim_feedforward = 4 * embed_dim (2048)
+VIT_LN_EPS = 1e-5
+VIT_DROPOUT = 0.1           # TransformerEncoder's default, on all four sites of a layer
+
+
+def _ln(sd, key, c):
+    sd[key + ".weight"] = ((c,), "ln_w")
+    sd[key + ".bias"] = ((c,), "ln_b")
+
+
+def vit_tower_sd(sd, prefix, hw, patch, embed_dim, depth, heads=None):
+    """AudioViTEncoder / ViTEncoder state dict under ``prefix``: the two nn.Parameters of the
+    module itself precede its submodules' keys."""
+    E, T = embed_dim, (hw // patch) ** 2 + 1
+    sd[f"{prefix}.cls_token"] = ((1, 1, E), "tok")
+    sd[f"{prefix}.pos_embed"] = ((1, T, E), "tok")
+    _dense(sd, f"{prefix}.patch_embed.projection", E, 1, patch)
+    for i in range(depth):
+        l = f"{prefix}.transformer.layers.{i}"
+        sd[f"{l}.self_attn.in_proj_weight"] = ((3 * E, E), "attn_w")
+        sd[f"{l}.self_attn.in_proj_bias"] = ((3 * E,), "attn_b")
+        sd[f"{l}.self_attn.out_proj.weight"] = ((E, E), "w")
+        sd[f"{l}.self_attn.out_proj.bias"] = ((E,), "attn_b")
+        _dense(sd, f"{l}.linear1", VIT_MLP_RATIO * E, E)
+        _dense(sd, f"{l}.linear2", E, VIT_MLP_RATIO * E)
+        _ln(sd, f"{l}.norm1", E)
+        _ln(sd, f"{l}.norm2", E)
+    _ln(sd, f"{prefix}.transformer.norm", E)
+
+
+def spectrogram_vit_sd(sd, prefix, out_dim):
+    vit_tower_sd(sd, f"{prefix}.encoder.0", **VIT_AUDIO)
+    _dense(sd, f"{prefix}.encoder.1", out_dim, VIT_AUDIO["embed_dim"])
+
+
+# UNIMODAL_MODEL_MAP encoders on the ViT tower (avdino/vit.py), kept apart from UNI_ENCODERS,
+# whose entries are all conv stacks:
+#   kind -> (modality, tower prefix relative to the encoder's, tower dimensions,
+#            [Linear keys after the tower], state-dict builder)
+VIT_ENCODERS = {
+    "spectrogram_vit": ("audio", "encoder.0", VIT_AUDIO, ["encoder.1"], spectrogram_vit_sd),
+}
+
+
+def uni_kinds():
+    """Every unimodal encoder kind the engine runs (conv stacks and ViT towers)."""
+    return tuple(UNI_ENCODERS) + tuple(VIT_ENCODERS)
+
+
+def uni_modality(kind):
+    kind = UNI_ALIASES.get(kind, kind)
+    return (VIT_ENCODERS[kind] if kind in VIT_ENCODERS else UNI_ENCODERS[kind])[0]
+
 
 def unimodal_dino_sd(kind, D, P):
-    """UniModalDINO (models/dino.py:1257-1297) state dict over an UNI_ENCODERS kind."""
+    """UniModalDINO (models/dino.py:1257-1297) state dict over an UNI_ENCODERS or VIT_ENCODERS
+    kind."""
     kind = UNI_ALIASES.get(kind, kind)
-    build = UNI_ENCODERS[kind][3]
+    build = VIT_ENCODERS[kind][4] if kind in VIT_ENCODERS else UNI_ENCODERS[kind][3]
     sd = OrderedDict()
     sd["center"] = ((1, P), "center")
     build(sd, "student", D)
