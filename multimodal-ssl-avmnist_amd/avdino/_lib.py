@@ -5,165 +5,71 @@ architecture, importing this module raises, so nothing can silently run a CPU pa
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AVDINO_LIB", os.path.join(_HERE, "libavdino.so"))
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "avdino.h"))
 
 F32, BF16 = 0, 1
 
-P = ctypes.c_void_p
-I = ctypes.c_int
-L = ctypes.c_longlong
-F = ctypes.c_float
-U64 = ctypes.c_ulonglong
-D = ctypes.c_double
-
-# name -> argtypes (restype is always c_int except where noted)
-PROTOS = {
-    "avd_version": [],
-    "avd_set_options": [P],
-    "avd_get_options": [P],
-    "avd_bn_finalize": [P, I, I, I, L, P, P, F, F, P, P, P, P, P, P, P, I, P],
-    "avd_bn_bwd_finalize": [P, I, I, I, L, P, P, P, P, P, P, P, I, P],
-    "avd_gemm": [I, I, I, P, L, L, P, L, L, P, L, P, F, F, I, P, L, P],
-    "avd_gemm_ws_elems": [I, I, I, I],
-    "avd_linear_bwd": [I, I, I, P, L, P, L, P, P, P, L, P, I, I, P, L, P],
-    "avd_linear_bwd_ws_elems": [I, I, I, I],
-    "avd_linear_hwc_ws_elems": [I, I, I],
-    "avd_linear_weight_hwc": [I, P, P, P, P, P, P],
-    "avd_linear_fwd_hwc": [I, I, I, I, P, P, P, P, L, P, L, P],
-    "avd_linear_bwd_hwc": [I, I, I, I, P, L, P, P, P, P, P, I, P, L, P],
-    "avd_cl_weight_elems": [I, I, I, I],
-    "avd_cl_weight_layout": [P, P, I, I, I, I, I, P],
-    "avd_cl_weight_layout_batch": [I, P, P, P, P, P, P, I, P],
-    "avd_cl_stat_rows": [I, I, I, I, I, I, I],
-    "avd_cl_conv_fwd": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
-    "avd_cl_stat_pivot": [I, I, I, I, I, I, I],
-    "avd_cl_conv_fwd_pv": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
-    "avd_cl_conv_dgrad": [P, P, P, I, I, I, I, I, I, I, I, P],
-    "avd_cl_wgrad_chunks": [I, I, I, I],
-    "avd_cl_conv_wgrad": [P, P, I, P, I, I, I, I, I, I, I, P],
-    "avd_cl_bn_bwd_reduce_pooled": [P, I, P, P, I, P, P, P, P, P, I, I, I, I, I, P],
-    "avd_cl_c1_moment_cols": [I, I],
-    "avd_cl_c1_codes_rows": [I, I, I, I],
-    "avd_cl_c1_codes_cols": [],
-    "avd_cl_c1_apply_codes": [P, P, P, P, P, P, P, I, I, I, I, P],
-    "avd_cl_c1_moments_codes": [P, P, P, P, I, I, I, I, P],
-    "avd_cl_c1_codes_combine": [P, P, P, P, P, P, L, P, P, P, P, P, I, P],
-    "avd_cl_c1r5_codes_rows": [I, I, I, I],
-    "avd_cl_c1r5_codes_cols": [],
-    "avd_cl_c1r5_apply_codes": [P, P, P, P, P, P, P, I, I, I, I, P],
-    "avd_cl_c1r5_stats_rows": [I, I, I, I],
-    "avd_cl_c1r5_stats": [P, P, P, P, I, I, I, I, P],
-    "avd_cl_c1r5_moments_codes": [P, P, P, P, I, I, I, I, P],
-    "avd_cl_c1r5_codes_combine": [P, P, P, P, P, P, L, P, P, P, P, P, I, P],
-    "avd_counters_add": [P, P, P, I, P],
-    "avd_mark": [P, I, P],
-    "avd_mark_span": [P, I, I, P],
-    "avd_cl_bn_relu_pool": [P, I, P, P, P, I, I, I, I, I, I, P],
-    "avd_cl_bn_relu_pool_codes": [P, P, P, P, P, I, I, I, I, I, P],
-    "avd_cl_bn_bwd_rows": [I, I, I, I, I],
-    "avd_cl_bn_bwd_reduce": [P, I, P, I, P, P, P, P, P, I, I, I, I, I, P],
-    "avd_cl_bn_bwd_apply": [P, I, P, I, P, P, P, P, I, I, I, I, I, P],
-    "avd_cl_apply_wgrad_slabs": [I, I, I, I, I, I, I, I],
-    "avd_cl_c1_recompute_rows": [I, I, I, I, I, I, I, I, I, I],
-    "avd_cl_c1_recompute": [I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
-    "avd_cl_c1_recompute_combine": [P, P, P, P, P, I, I, I, P],
-    "avd_cl_bn_bwd_apply_wgrad": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
-    "avd_lds_poison": [P],
-    "avd_xent_fused_ws": [I, I, I],
-    "avd_xent_fused": [P, P, I, I, I, I, I, I, I, I, F, F, P, P, P, P, L, P],
-    "avd_xattn_fwd": [P, L, L, P, L, L, P, L, L, P, L, L, P, L, L, P, I, I, I, I, F, P],
-    "avd_xattn_bwd_ws": [I, I, I, I],
-    "avd_xattn_bwd": [P, L, L, P, L, L, P, L, L, P, L, L, P, P, L, L, P, L, L, P, L, L, P, L,
-                      I, I, I, I, F, P],
-    "avd_gate_fwd": [P, L, P, P, P, L, I, I, P],
-    "avd_gate_bwd_ws": [I, I],
-    "avd_gate_bwd": [P, L, P, L, P, P, P, L, P, P, P, L, I, I, P],
-    "avd_softmax_rows_fwd": [P, L, I, I, P],
-    "avd_softmax_rows_bwd": [P, L, P, L, I, I, P],
-    "avd_lstm_ws": [I, I, I, P, P],
-    "avd_lstm_fwd": [P, P, P, P, P, I, I, I, I, I, P],
-    "avd_lstm_bwd": [P, P, P, P, P, I, I, I, I, P],
-    "avd_cast": [P, I, P, I, L, P],
-    "avd_mhsa_fwd": [P, L, P, L, P, L, P, L, P, I, I, I, I, I, F, F, U64, P, P],
-    "avd_mhsa_bwd_ws": [I, I, I, I],
-    "avd_mhsa_bwd": [P, L, P, L, P, L, P, L, P, P, L, P, L, P, L, P, L, I, I, I, I, I, F, F, U64, P, P],
-    "avd_ln_fwd": [P, L, P, L, P, P, P, L, P, P, P, I, I, F, F, U64, P, P],
-    "avd_ln_bwd_ws": [I, I],
-    "avd_ln_bwd": [P, L, P, P, P, P, P, L, P, L, P, P, P, L, I, I, F, U64, P, P],
-    "avd_gelu_fwd": [P, P, L, I, F, U64, P, P],
-    "avd_gelu_bwd": [P, P, P, L, I, F, U64, P, P],
-    "avd_vit_patchify": [P, I, P, I, I, I, I, P],
-    "avd_vit_tokens_fwd": [P, P, P, P, I, I, I, P],
-    "avd_vit_tokens_bwd": [P, P, I, I, I, P],
-    "avd_cl_layer_bwd_slabs": [I, I, I, I, I, I, I, I],
-    "avd_cl_layer_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
-    "avd_cl_layer_bwd_codes": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
-    "avd_sum_rows": [P, I, I, L, P, I, P],
-    "avd_sum_rows_chunks": [I, I],
-    "avd_sum_rows_split": [P, I, I, L, P, I, P, L, P],
-    "avd_colstats_parts": [I],
-    "avd_colstats": [P, I, I, I, P, P, P],
-    "avd_act_fwd": [P, P, I, P, P, I, I, I, F, U64, P],
-    "avd_act_bwd": [P, P, P, I, P, P, I, I, I, F, U64, P],
-    "avd_act_fwd_dev": [P, P, I, P, P, I, I, I, F, U64, P, P],
-    "avd_act_bwd_dev": [P, P, P, I, P, P, I, I, I, F, U64, P, P],
-    "avd_step_begin": [P, P, P, D, D, U64, P],
-    "avd_adam_dev": [P, P, P, P, L, P, F, F, F, F, P],
-    "avd_adamw_dev": [P, P, P, P, L, P, F, F, F, F, P],
-    "avd_bn1d_bwd_reduce": [P, P, P, P, I, I, I, P, P],
-    "avd_bn1d_act_bwd_reduce": [P, P, P, P, P, P, P, I, I, I, F, U64, P, P, P],
-    "avd_bn1d_bwd_apply": [P, P, P, P, I, I, I, P],
-    "avd_dino_loss": [P, P, P, I, I, I, I, F, F, F, I, P, P, P, P, P],
-    "avd_mse_loss": [P, P, I, I, P, P, P, P],
-    "avd_l2norm_fwd": [P, P, P, I, I, P],
-    "avd_l2norm_bwd": [P, P, P, P, I, I, P],
-    "avd_softmax_xent": [P, L, I, I, P, I, I, I, I, F, P, P, L, I, P],
-    "avd_cosine_consistency": [P, I, I, I, F, P, P, P],
-    "avd_ema": [P, P, L, F, P],
-    "avd_adam": [P, P, P, P, L, F, F, F, F, F, F, F, P],
-    "avd_adamw": [P, P, P, P, L, F, F, F, F, F, F, F, P],
-    "avd_axpy": [P, P, L, F, P],
-    "avd_bn_eval_coef": [P, P, P, P, F, I, P, P, P],
-    "avd_c3_eval_serves": [I, I, I, I, I, I],
-    "avd_c3_conv_eval": [P, P, P, P, P, P, I, I, I, I, I, I, P],
-    "avd_argmax_correct": [P, L, I, I, P, P, P],
-    "avd_sum": [P, I, F, P, P],
-    "avd_stage_views": [P, I, P, I, P, I, I, P, I, P],
-    "avd_augment_views": [P, P, L, I, I, I, I, P, P, P, I, I, U64, I, P, P],
-    "avd_augment_views_dt": [P, P, L, I, I, I, I, P, P, P, I, I, U64, I, P, I, P],
-    "avd_augment_views_lds_check": [P, P, I, I, I, I, P, P, P, I, I, U64, I, P, P, P, P],
-    "avd_augment_views_nolds": [P, P, I, I, I, I, P, P, P, I, I, U64, I, P, P],
-    "avd_augment_views_seq": [P, P, L, I, I, I, I, P, P, P, I, I, U64, I, P, I, P, I, P],
-    "avd_augment_records": [P, I, I, I, I, I, U64, P, P, I, P],
-    "avd_augment_views_x": [P, P, L, I, I, I, I, P, P, P, I, I, U64, I, P, I, P, I, P, P],
-    "avd_augment_records_x": [P, I, I, I, I, I, U64, P, P, I, P, P],
-    "avd_row_sqnorm": [P, I, I, P, P],
-    "avd_knn_select": [P, L, P, I, I, I, P, P, I, P, I, P, P, P],
-    "avd_argmax_rows": [P, L, I, I, P, P],
-    "avd_cl_c1_gram_cols": [],
-    "avd_cl_c1_gram": [P, P, I, I, I, I, P],
-    "avd_cl_c1_gram_finalize": [P, P, P, P, P, L, F, F, P, P, P, P, P, P, I, P],
-    "avd_cl_c1_moments_codes_ng": [P, P, P, P, I, I, I, I, P],
-    "avd_cl_c1_codes_combine_gram": [P, P, P, P, P, P, P, L, P, P, P, P, P, I, P],
-    "avd_cl_c1r3_codes_rows": [I, I, I, I, I],
-    "avd_cl_c1r3_codes_cols": [I],
-    "avd_cl_c1r3_apply_codes": [P, P, P, P, P, P, P, I, I, I, I, I, P],
-    "avd_cl_c1r3_moments_codes": [P, P, P, P, P, I, I, I, I, I, P],
-    "avd_cl_c1r3_codes_combine": [P, P, P, P, P, P, L, P, P, P, P, P, I, I, P],
-    "avd_mx_weight_bytes": [I, I, I, I],
-    "avd_mx_scale_bytes": [I, I, I, I],
-    "avd_mx_weight_layout": [P, P, P, I, I, I, I, P],
-    "avd_mx_weight_layout_batch": [I, P, P, P, P, P, P, P, P],
-    "avd_mx_conv_serves": [I, I, I, I, I, I, I],
-    "avd_mx_conv_ns": [I, I, I, I, I, I, I],
-    "avd_mx_stat_rows": [I, I, I, I, I, I, I],
-    "avd_mx_conv_fwd": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P],
-    "avd_mx_conv_dgrad": [P, P, P, P, I, I, I, I, I, I, I, P],
-    "avd_mx_wgrad_chunks": [I, I, I, I, I, I],
-    "avd_mx_conv_wgrad": [P, P, P, I, I, I, I, I, I, I, P],
+# the header's scalar types (a pointer of any kind is c_void_p)
+_SCALARS = {
+    "int": ctypes.c_int,
+    "avd_dtype": ctypes.c_int,
+    "long long": ctypes.c_longlong,
+    "unsigned long long": ctypes.c_ulonglong,
+    "float": ctypes.c_float,
+    "double": ctypes.c_double,
 }
+_RETURNS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "const char*": ctypes.c_char_p}
+
+
+def _param_type(fn, text):
+    if "*" in text:
+        return ctypes.c_void_p
+    words = [w for w in text.split() if w != "const"]
+    for t in (" ".join(words), " ".join(words[:-1])):     # without / with a parameter name
+        if t in _SCALARS:
+            return _SCALARS[t]
+    raise ImportError(f"avdino.h: {fn}: unrecognised parameter type {text!r}")
+
+
+def parse_header(text):
+    """(PROTOS, RESTYPES) of a header in include/avdino.h's C subset: once comments, preprocessor
+    lines and the typedef / enum / extern "C" scaffolding are gone, every statement is
+    ``RET avd_name(PARAMS);`` over the types above.  Anything else raises ImportError."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
+    text = re.sub(r"\b(typedef\s+)?(enum|struct)\b[^{};()]*\{[^{}]*\}[^{};()]*;", " ", text)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    protos, restypes = {}, {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.replace("}", " ").split())
+        if not stmt:
+            continue
+        m = re.fullmatch(r"(.+?)\b(avd_\w+) ?\(([^()]*)\)", stmt)
+        if m is None:
+            raise ImportError(f"avdino.h: not a function declaration: {stmt!r}")
+        ret, fn, params = m.group(1).replace(" *", "*").strip(), m.group(2), m.group(3).strip()
+        if ret not in _RETURNS:
+            raise ImportError(f"avdino.h: {fn}: unrecognised return type {ret!r}")
+        restypes[fn] = _RETURNS[ret]
+        protos[fn] = [] if params == "void" else [_param_type(fn, a.strip()) for a in params.split(",")]
+    return protos, restypes
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise ImportError(f"include/avdino.h not readable at {HEADER_PATH} ({e}): the ctypes "
+                          f"prototypes are taken from it") from None
+
+
+# name -> argtypes and name -> restype of every function the header declares
+PROTOS, RESTYPES = parse_header(_read_header())
 
 
 class AvdError(RuntimeError):
@@ -180,15 +86,7 @@ def _load():
     for name, args in PROTOS.items():
         fn = getattr(lib, name)
         fn.argtypes = args
-        fn.restype = ctypes.c_int
-    lib.avd_gemm_ws_elems.restype = ctypes.c_longlong
-    lib.avd_linear_hwc_ws_elems.restype = ctypes.c_longlong
-    lib.avd_mhsa_bwd_ws.restype = ctypes.c_longlong
-    lib.avd_ln_bwd_ws.restype = ctypes.c_longlong
-    lib.avd_mx_weight_bytes.restype = ctypes.c_longlong
-    lib.avd_mx_scale_bytes.restype = ctypes.c_longlong
-    lib.avd_last_error.argtypes = []
-    lib.avd_last_error.restype = ctypes.c_char_p
+        fn.restype = RESTYPES[name]
     return lib
 
 

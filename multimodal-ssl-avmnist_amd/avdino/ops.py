@@ -185,6 +185,26 @@ def _need(cond, msg):
         raise ValueError(msg)
 
 
+def _rows(t, off, ld, rows, cols, what, dtype=torch.float32, align=1, extra=0):
+    """Address of a strided block of rows inside a contiguous tensor: row r is the `cols`
+    elements at element off + r * ld (ld None: cols); `extra` more elements past the last row
+    belong to it for an operand with a second stride; `align`: what ld and off must be multiples
+    of.  Everything the kernel may touch must lie inside t (no device OOB)."""
+    ld = cols if ld is None else ld
+    _need(t.dtype == dtype and t.is_contiguous(), f"{what}: contiguous {dtype}")
+    _need(off >= 0 and ld >= cols, f"{what}: offset >= 0, ld >= {cols}")
+    _need(ld % align == 0 and off % align == 0, f"{what}: ld / offset multiples of {align}")
+    _need(off + extra + (rows - 1) * ld + cols <= t.numel(), f"{what} bounds")
+    return t.data_ptr() + t.element_size() * off
+
+
+def _flat(t, n, what, dtype=torch.float32):
+    """Address of a contiguous tensor of `dtype` with at least n elements."""
+    _need(t is not None and t.dtype == dtype and t.is_contiguous() and t.numel() >= n,
+          f"{what}: contiguous {dtype} with >= {n} elements")
+    return t.data_ptr()
+
+
 # ---------------------------------------------------------------- BatchNorm statistics
 def bn_finalize(parts, G, R, C, count, gamma, beta, mean, invstd, scale, shift, rm=None, rv=None,
                 eps=1e-5, momentum=0.1, pivot=None, pivot_gs=None):
@@ -265,37 +285,23 @@ def linear_bwd(dout, x, w, dw, db, dx, rows, dout_ld=None, dout_off=0, x_ld=None
         _need(dx is not None, "linear_bwd: nothing to compute")
         gemm(rows, In, O, dout, dout_ld, 1, w, In, 1, dx, dx_ld, a_off=dout_off, c_off=dx_off, mode=mode)
         return
-    if dx is not None and mode in (GEMM_F32_MFMA, GEMM_BF16_MFMA) and PAIR_BWD:
-        # dW, dX and the bias gradient on the same launches (avd_linear_bwd)
-        for t in (dout, x, w, dw, dx):
-            _need(t.dtype == torch.float32 and t.is_contiguous(), "linear_bwd operands are contiguous f32")
-        _need(dout_off + (rows - 1) * dout_ld + O <= dout.numel(), "linear_bwd dout bounds")
-        _need(x_off + (rows - 1) * x_ld + In <= x.numel(), "linear_bwd x bounds")
-        _need(dx_off + (rows - 1) * dx_ld + In <= dx.numel(), "linear_bwd dx bounds")
-        _need(dw.numel() >= O * In, "linear_bwd dw size")
+    if mode in (GEMM_F32_MFMA, GEMM_BF16_MFMA) and PAIR_BWD:
+        # dW and the bias gradient on one launch and its reduce (avd_linear_bwd), with dx on the
+        # same launches; without it, the paired launch's dW grid alone
+        a = [_rows(dout, dout_off, dout_ld, rows, O, "linear_bwd dout"), dout_ld,
+             _rows(x, x_off, x_ld, rows, In, "linear_bwd x"), x_ld]
+        if dx is not None:
+            a += [_flat(w, O * In, "linear_bwd w"), _flat(dw, O * In, "linear_bwd dw"),
+                  _rows(dx, dx_off, dx_ld, rows, In, "linear_bwd dx"), dx_ld]
+            key, which, nb, fl = "linear_bwd", 3, 2 * rows * O + 2 * rows * In + 2 * O * In, 4 * rows * O * In
+        else:
+            a += [None, _flat(dw, O * In, "linear_bwd dw"), None, In]
+            key, which, nb, fl = "linear_bwd_dw", 1, rows * O + rows * In + O * In, 2 * rows * O * In
+        _need(db is None or db.numel() >= O, "linear_bwd db size")
         nws = lib.avd_linear_bwd_ws_elems(rows, O, In, mode)   # > 0: includes the bias partials
         ws = _gemm_workspace(dout.device, nws)
-        _need(db is None or db.numel() >= O, "linear_bwd db size")
-        _timed(f"linear_bwd[{rows}x{O}x{In} m{mode}]",
-               4 * (2 * rows * O + rows * In + O * In + O * In + rows * In), 4 * rows * O * In,
-               lambda: call("avd_linear_bwd", rows, O, In, dout.data_ptr() + 4 * dout_off, dout_ld,
-                            x.data_ptr() + 4 * x_off, x_ld, p(w), p(dw),
-                            dx.data_ptr() + 4 * dx_off, dx_ld, p(db), mode, 3, p(ws), nws, stream()))
-        return
-    if dx is None and mode in (GEMM_F32_MFMA, GEMM_BF16_MFMA) and PAIR_BWD:
-        # the weight gradient alone (+ db) on the paired launch's dW grid and its reduce
-        for t in (dout, x, dw):
-            _need(t.dtype == torch.float32 and t.is_contiguous(), "linear_bwd operands are contiguous f32")
-        _need(dout_off + (rows - 1) * dout_ld + O <= dout.numel(), "linear_bwd dout bounds")
-        _need(x_off + (rows - 1) * x_ld + In <= x.numel(), "linear_bwd x bounds")
-        _need(dw.numel() >= O * In and (db is None or db.numel() >= O), "linear_bwd dw / db size")
-        nws = lib.avd_linear_bwd_ws_elems(rows, O, In, mode)
-        ws = _gemm_workspace(dout.device, nws)
-        _timed(f"linear_bwd_dw[{rows}x{O}x{In} m{mode}]", 4 * (rows * O + rows * In + O * In),
-               2 * rows * O * In,
-               lambda: call("avd_linear_bwd", rows, O, In, dout.data_ptr() + 4 * dout_off, dout_ld,
-                            x.data_ptr() + 4 * x_off, x_ld, None, p(dw), None, In, p(db), mode, 1,
-                            p(ws), nws, stream()))
+        _timed(f"{key}[{rows}x{O}x{In} m{mode}]", 4 * nb, fl,
+               lambda: call("avd_linear_bwd", rows, O, In, *a, p(db), mode, which, p(ws), nws, stream()))
         return
     # dW[o, i] = sum_r dout[r, o] x[r, i]: A = dout^T (M=O, K=rows), B = x (K=rows, N=In)
     gemm(O, In, rows, dout, 1, dout_ld, x, x_ld, 1, dw, In, a_off=dout_off, b_off=x_off, mode=mode)
@@ -310,17 +316,16 @@ def linear_bwd(dout, x, w, dw, db, dx, rows, dout_ld=None, dout_off=0, x_ld=None
 def linear_weight_hwc(entries):
     """entries: [(W f32 [O, C*HW] in (c,h,w) column order, Wp bf16 [O*HW*C], C, HW)] (<= 4) ->
     Wp = W with its columns in (h, w, c) order, one launch."""
-    import ctypes as _ct
     n = len(entries)
     _need(0 < n <= 4, "linear_weight_hwc batch size")
     for W, Wp, C, HW in entries:
         _need(W.dtype == torch.float32 and W.is_contiguous() and W.shape[1] == C * HW, "hwc W")
         _need(Wp.dtype == torch.bfloat16 and Wp.numel() >= W.numel(), "hwc Wp")
-    ws = (_ct.c_void_p * n)(*[e[0].data_ptr() for e in entries])
-    wps = (_ct.c_void_p * n)(*[e[1].data_ptr() for e in entries])
-    Os = (_ct.c_int * n)(*[e[0].shape[0] for e in entries])
-    Cs = (_ct.c_int * n)(*[e[2] for e in entries])
-    HWs = (_ct.c_int * n)(*[e[3] for e in entries])
+    ws = (ctypes.c_void_p * n)(*[e[0].data_ptr() for e in entries])
+    wps = (ctypes.c_void_p * n)(*[e[1].data_ptr() for e in entries])
+    Os = (ctypes.c_int * n)(*[e[0].shape[0] for e in entries])
+    Cs = (ctypes.c_int * n)(*[e[2] for e in entries])
+    HWs = (ctypes.c_int * n)(*[e[3] for e in entries])
     call("avd_linear_weight_hwc", n, ws, wps, Os, Cs, HWs, stream())
 
 
@@ -329,15 +334,13 @@ def linear_fwd_hwc(feat, wp, b, out, rows, O, C, HW, out_ld=None, out_off=0):
     Linear over the last conv block's NHWC pooled map)."""
     In = C * HW
     out_ld = O if out_ld is None else out_ld
-    _need(feat.dtype == torch.bfloat16 and feat.numel() >= rows * In, "hwc fwd feat")
-    _need(wp.dtype == torch.bfloat16 and wp.numel() >= O * In, "hwc fwd Wp")
-    _need(out.dtype == torch.float32 and out_off + (rows - 1) * out_ld + O <= out.numel(), "hwc fwd out")
+    a = [_flat(feat, rows * In, "hwc fwd feat", torch.bfloat16), _flat(wp, O * In, "hwc fwd Wp", torch.bfloat16),
+         p(b), _rows(out, out_off, out_ld, rows, O, "hwc fwd out"), out_ld]
     nws = lib.avd_linear_hwc_ws_elems(rows, O, In)
     ws = _gemm_workspace(out.device, nws)
     _timed(f"linear_fwd_hwc[{rows}x{O}x{In}]", 2 * rows * In + 2 * O * In + 4 * rows * O,
            2 * rows * O * In,
-           lambda: call("avd_linear_fwd_hwc", rows, O, C, HW, p(feat), p(wp), p(b),
-                        out.data_ptr() + 4 * out_off, out_ld, p(ws), nws, stream()))
+           lambda: call("avd_linear_fwd_hwc", rows, O, C, HW, *a, p(ws), nws, stream()))
 
 
 def linear_bwd_hwc(dout, feat, wp, dw, db, dx, rows, O, C, HW, dout_ld=None, dout_off=0, which=3):
@@ -346,11 +349,9 @@ def linear_bwd_hwc(dout, feat, wp, dw, db, dx, rows, O, C, HW, dout_ld=None, dou
     dX alone)."""
     In = C * HW
     dout_ld = O if dout_ld is None else dout_ld
-    _need(dout.dtype == torch.float32 and dout_off + (rows - 1) * dout_ld + O <= dout.numel(), "hwc bwd dout")
-    _need(feat.dtype == torch.bfloat16 and feat.numel() >= rows * In, "hwc bwd feat")
-    _need(wp.dtype == torch.bfloat16 and wp.numel() >= O * In, "hwc bwd Wp")
-    _need(dw.dtype == torch.float32 and dw.numel() >= O * In, "hwc bwd dW")
-    _need(dx.dtype == torch.bfloat16 and dx.numel() >= rows * In, "hwc bwd dX")
+    a = [_rows(dout, dout_off, dout_ld, rows, O, "hwc bwd dout"), dout_ld,
+         _flat(feat, rows * In, "hwc bwd feat", torch.bfloat16), _flat(wp, O * In, "hwc bwd Wp", torch.bfloat16),
+         _flat(dw, O * In, "hwc bwd dW"), p(db), _flat(dx, rows * In, "hwc bwd dX", torch.bfloat16)]
     _need(db is None or db.numel() >= O, "hwc bwd db")
     nws = lib.avd_linear_hwc_ws_elems(rows, O, In)
     ws = _gemm_workspace(dout.device, nws)
@@ -358,8 +359,7 @@ def linear_bwd_hwc(dout, feat, wp, dw, db, dx, rows, O, C, HW, dout_ld=None, dou
     nb = {3: 4 * 2 * rows * O + 2 * 2 * rows * In + 2 * O * In + 4 * O * In,
           2: 4 * rows * O + 2 * rows * In + 2 * O * In, 1: 4 * rows * O + 2 * rows * In + 4 * O * In}[which]
     _timed(f"linear_bwd_hwc{part}[{rows}x{O}x{In}]", nb, (4 if which == 3 else 2) * rows * O * In,
-           lambda: call("avd_linear_bwd_hwc", rows, O, C, HW, dout.data_ptr() + 4 * dout_off, dout_ld,
-                        p(feat), p(wp), p(dw), p(db), p(dx), which, p(ws), nws, stream()))
+           lambda: call("avd_linear_bwd_hwc", rows, O, C, HW, *a, which, p(ws), nws, stream()))
 
 
 # ---------------------------------------------------------------- channels-last conv blocks
@@ -1049,29 +1049,28 @@ def xent_fused_ws(R, C, P):
 def xent_fused(q, k, R, C, P, Bh, tgt, msk, inv_t, gscale, loss, dq, dk, ws):
     """Softmax cross-entropy over S = inv_t q k^T with per-half targets / masks, loss rows and
     both gradients, without materialising S (avd_xent_fused, xent.hip; bf16 MFMA)."""
-    for t, n in ((q, R * P), (k, C * P), (dq, R * P), (dk, C * P), (loss, R)):
-        _need(t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n, "xent operand")
-    _need(ws.dtype == torch.float32 and ws.numel() >= xent_fused_ws(R, C, P), "xent workspace")
+    qp, kp, dqp, dkp, lp = (_flat(t, n, "xent operand")
+                            for t, n in ((q, R * P), (k, C * P), (dq, R * P), (dk, C * P), (loss, R)))
+    wp = _flat(ws, xent_fused_ws(R, C, P), "xent workspace")
     fl = 4 * 2 * R * C * P
     _timed(f"xent_fused[{R}x{C}x{P}]", 4 * (2 * R * P + 2 * C * P + R), fl,
-           lambda: call("avd_xent_fused", p(q), p(k), R, C, P, Bh, int(tgt[0]), int(tgt[1]), int(msk[0]),
-                        int(msk[1]), inv_t, gscale, p(loss), p(dq), p(dk), p(ws), ws.numel(), stream()))
+           lambda: call("avd_xent_fused", qp, kp, R, C, P, Bh, int(tgt[0]), int(tgt[1]), int(msk[0]),
+                        int(msk[1]), inv_t, gscale, lp, dqp, dkp, wp, ws.numel(), stream()))
 
 
 # ---------------------------------------------------------------- fusion-encoder mix stage
 XATTN_DIMS = (32, 64, 128, 256, 512)     # encoder_output_dim the fused attention serves
 
 
-def _xmat(m, dirs, groups, B, E, what):
-    """A strided attention operand (tensor, element offset, ld, direction stride): group g of
-    direction d = rows at off + d ds + g B ld.  Checks that everything the kernel may touch
-    lies inside the tensor; returns (address, ld, ds)."""
-    t, off, ld, ds = m
-    _need(t.dtype == torch.float32 and t.is_contiguous(), f"xattn {what}: contiguous f32")
-    _need(ld >= E and ld % 4 == 0 and ds % 4 == 0 and off % 4 == 0 and ds >= 0 and off >= 0,
-          f"xattn {what}: ld >= E, ld / offset / direction stride multiples of 4")
-    _need(off + (dirs - 1) * ds + (groups * B - 1) * ld + E <= t.numel(), f"xattn {what} bounds")
-    return t.data_ptr() + 4 * off, ld, ds
+def _xargs(ms, dirs, groups, B, E):
+    """The (address, ld, direction stride) arguments of strided attention operands
+    ((tensor, element offset, ld, direction stride), name): group g of direction d = the B rows
+    at off + d ds + g B ld, all of which must lie inside the tensor."""
+    a = []
+    for (t, off, ld, ds), what in ms:
+        _need(ds >= 0 and ds % 4 == 0, f"xattn {what}: direction stride a multiple of 4 (>= 0)")
+        a += [_rows(t, off, ld, groups * B, E, f"xattn {what}", align=4, extra=(dirs - 1) * ds), ld, ds]
+    return a
 
 
 def _xdims(dirs, groups, B, E):
@@ -1083,13 +1082,11 @@ def xattn_fwd(q, k, v, x, out, lse, dirs, groups, B, E, scale):
     """OUT = X + softmax(scale Q K^T) V per (direction, group) in one launch (avd_xattn_fwd);
     operands are (tensor, offset, ld, direction stride); lse [dirs*groups*B] or None."""
     _xdims(dirs, groups, B, E)
-    a = [_xmat(m, dirs, groups, B, E, n) for m, n in ((q, "q"), (k, "k"), (v, "v"), (x, "x"), (out, "out"))]
-    _need(lse is None or (lse.dtype == torch.float32 and lse.is_contiguous()
-                          and lse.numel() >= dirs * groups * B), "xattn lse size")
-    flat = [y for m in a for y in m]
+    a = _xargs(((q, "q"), (k, "k"), (v, "v"), (x, "x"), (out, "out")), dirs, groups, B, E)
     n = dirs * groups * B
+    lp = None if lse is None else _flat(lse, n, "xattn lse")
     _timed(f"xattn_fwd[{dirs}x{groups}x{B}x{E}]", 4 * 5 * n * E, 4 * n * B * E,
-           lambda: call("avd_xattn_fwd", *flat, p(lse), dirs, groups, B, E, scale, stream()))
+           lambda: call("avd_xattn_fwd", *a, lp, dirs, groups, B, E, scale, stream()))
 
 
 def xattn_bwd_ws(dirs, groups, B, E):
@@ -1100,21 +1097,12 @@ def xattn_bwd_ws(dirs, groups, B, E):
 def xattn_bwd(dout, q, k, v, lse, dq, dk, dv, ws, dirs, groups, B, E, scale):
     """dQ, dK, dV of the attention term from dOUT, Q, K, V and the forward's lse (avd_xattn_bwd)."""
     _xdims(dirs, groups, B, E)
-    a = [_xmat(m, dirs, groups, B, E, n) for m, n in ((dout, "dout"), (q, "q"), (k, "k"), (v, "v"))]
-    g = [_xmat(m, dirs, groups, B, E, n) for m, n in ((dq, "dq"), (dk, "dk"), (dv, "dv"))]
+    a = _xargs(((dout, "dout"), (q, "q"), (k, "k"), (v, "v")), dirs, groups, B, E)
+    g = _xargs(((dq, "dq"), (dk, "dk"), (dv, "dv")), dirs, groups, B, E)
     n = dirs * groups * B
-    _need(lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= n, "xattn lse size")
-    _need(ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= xattn_bwd_ws(dirs, groups, B, E),
-          "xattn workspace")
+    a += [_flat(lse, n, "xattn lse"), *g, _flat(ws, xattn_bwd_ws(dirs, groups, B, E), "xattn workspace")]
     _timed(f"xattn_bwd[{dirs}x{groups}x{B}x{E}]", 4 * 7 * n * E, 14 * n * B * E,
-           lambda: call("avd_xattn_bwd", *[y for m in a for y in m], p(lse), *[y for m in g for y in m],
-                        p(ws), ws.numel(), dirs, groups, B, E, scale, stream()))
-
-
-def _rows2e(t, off, ld, rows, E, what):
-    _need(t.dtype == torch.float32 and t.is_contiguous() and ld >= 2 * E and off >= 0
-          and off + (rows - 1) * ld + 2 * E <= t.numel(), f"gate {what} bounds")
-    return t.data_ptr() + 4 * off
+           lambda: call("avd_xattn_bwd", *a, ws.numel(), dirs, groups, B, E, scale, stream()))
 
 
 def gate_fwd(cat, gate_image, gate_audio, out, rows, E, cat_ld=None, cat_off=0, out_ld=None, out_off=0):
@@ -1123,8 +1111,8 @@ def gate_fwd(cat, gate_image, gate_audio, out, rows, E, cat_ld=None, cat_off=0, 
     out_ld = 2 * E if out_ld is None else out_ld
     _need(rows >= 1 and E >= 1, "gate shapes")
     _need(gate_image.numel() == 1 and gate_audio.numel() == 1, "gates are scalars")
-    call("avd_gate_fwd", _rows2e(cat, cat_off, cat_ld, rows, E, "cat"), cat_ld, p(gate_image), p(gate_audio),
-         _rows2e(out, out_off, out_ld, rows, E, "out"), out_ld, rows, E, stream())
+    call("avd_gate_fwd", _rows(cat, cat_off, cat_ld, rows, 2 * E, "gate cat"), cat_ld, p(gate_image),
+         p(gate_audio), _rows(out, out_off, out_ld, rows, 2 * E, "gate out"), out_ld, rows, E, stream())
 
 
 def gate_bwd_ws(rows, E):
@@ -1142,27 +1130,25 @@ def gate_bwd(dout, cat, gate_image, gate_audio, dcat, dgate_image, dgate_audio, 
     _need(rows >= 1 and E >= 1, "gate shapes")
     for g in (gate_image, gate_audio, dgate_image, dgate_audio):
         _need(g.numel() == 1 and g.dtype == torch.float32, "gates are f32 scalars")
-    _need(ws.dtype == torch.float32 and ws.numel() >= gate_bwd_ws(rows, E), "gate workspace")
-    call("avd_gate_bwd", _rows2e(dout, 0, dout_ld, rows, E, "dout"), dout_ld,
-         _rows2e(cat, 0, cat_ld, rows, E, "cat"), cat_ld, p(gate_image), p(gate_audio),
-         _rows2e(dcat, 0, dcat_ld, rows, E, "dcat"), dcat_ld, p(dgate_image), p(dgate_audio), p(ws),
+    wp = _flat(ws, gate_bwd_ws(rows, E), "gate workspace")
+    call("avd_gate_bwd", _rows(dout, 0, dout_ld, rows, 2 * E, "gate dout"), dout_ld,
+         _rows(cat, 0, cat_ld, rows, 2 * E, "gate cat"), cat_ld, p(gate_image), p(gate_audio),
+         _rows(dcat, 0, dcat_ld, rows, 2 * E, "gate dcat"), dcat_ld, p(dgate_image), p(dgate_audio), wp,
          ws.numel(), rows, E, stream())
 
 
 def softmax_rows_fwd(s, R, C, ld=None):
     ld = C if ld is None else ld
-    _need(s.dtype == torch.float32 and s.is_contiguous() and R >= 1 and C >= 1 and ld >= C
-          and (R - 1) * ld + C <= s.numel(), "softmax rows bounds")
-    call("avd_softmax_rows_fwd", p(s), ld, R, C, stream())
+    _need(R >= 1 and C >= 1, "softmax rows: R, C >= 1")
+    call("avd_softmax_rows_fwd", _rows(s, 0, ld, R, C, "softmax rows"), ld, R, C, stream())
 
 
 def softmax_rows_bwd(pr, dp, R, C, ldp=None, lddp=None):
     ldp = C if ldp is None else ldp
     lddp = C if lddp is None else lddp
-    for t, ld in ((pr, ldp), (dp, lddp)):
-        _need(t.dtype == torch.float32 and t.is_contiguous() and R >= 1 and C >= 1 and ld >= C
-              and (R - 1) * ld + C <= t.numel(), "softmax rows bounds")
-    call("avd_softmax_rows_bwd", p(pr), ldp, p(dp), lddp, R, C, stream())
+    _need(R >= 1 and C >= 1, "softmax rows: R, C >= 1")
+    call("avd_softmax_rows_bwd", _rows(pr, 0, ldp, R, C, "softmax rows p"), ldp,
+         _rows(dp, 0, lddp, R, C, "softmax rows dp"), lddp, R, C, stream())
 
 
 # ---------------------------------------------------------------- LSTM recurrence (lstm.hip)
@@ -1173,11 +1159,6 @@ LSTM_BLOCK = 16                           # sequences per workgroup
 def _lstm_dims(N, T, H):
     _need(H in LSTM_HIDDEN, f"lstm: hidden size must be one of {LSTM_HIDDEN} (got {H})")
     _need(N >= 1 and T >= 1, "lstm: N, T >= 1")
-
-
-def _lstm_f32(t, n, what):
-    _need(t is not None and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n,
-          f"lstm {what}: contiguous f32 with >= {n} elements")
 
 
 def lstm_ws(N, T, H):
@@ -1199,30 +1180,23 @@ def lstm_fwd(gx, whh_f, whh_r, out, save, N, T, H, bf16):
     gx [N, T, 2, 4H] (avd_lstm_fwd); save: the backward's state buffer, or None (not touched)."""
     _lstm_dims(N, T, H)
     ns, ng = lstm_ws(N, T, H)
-    _lstm_f32(gx, ng, "gx")
-    _lstm_f32(whh_f, 4 * H * H, "weight_hh")
-    _lstm_f32(whh_r, 4 * H * H, "weight_hh (reverse)")
-    _lstm_f32(out, N * 2 * H, "out")
-    if save is not None:
-        _lstm_f32(save, ns, "saved state")
+    a = [_flat(gx, ng, "lstm gx"), _flat(whh_f, 4 * H * H, "lstm weight_hh"),
+         _flat(whh_r, 4 * H * H, "lstm weight_hh (reverse)"), _flat(out, N * 2 * H, "lstm out"),
+         None if save is None else _flat(save, ns, "lstm saved state")]
     _timed(f"lstm_fwd[{N}x{T}x{H} bf{int(bool(bf16))}]", 4 * (ng + (ns if save is not None else 0)),
            2 * N * T * 2 * 4 * H * H,
-           lambda: call("avd_lstm_fwd", p(gx), p(whh_f), p(whh_r), p(out), p(save),
-                        int(save is not None), BF16 if bf16 else F32, N, T, H, stream()))
+           lambda: call("avd_lstm_fwd", *a, int(save is not None), BF16 if bf16 else F32, N, T, H, stream()))
 
 
 def lstm_bwd(dout, whh_f, whh_r, save, dg, N, T, H, bf16):
     """dg [N, T, 2, 4H] = gradient of gx from dout [N, 2H] (avd_lstm_bwd; the mean's 1/T inside)."""
     _lstm_dims(N, T, H)
     ns, ng = lstm_ws(N, T, H)
-    _lstm_f32(dout, N * 2 * H, "dout")
-    _lstm_f32(whh_f, 4 * H * H, "weight_hh")
-    _lstm_f32(whh_r, 4 * H * H, "weight_hh (reverse)")
-    _lstm_f32(save, ns, "saved state")
-    _lstm_f32(dg, ng, "dg")
+    a = [_flat(dout, N * 2 * H, "lstm dout"), _flat(whh_f, 4 * H * H, "lstm weight_hh"),
+         _flat(whh_r, 4 * H * H, "lstm weight_hh (reverse)"), _flat(save, ns, "lstm saved state"),
+         _flat(dg, ng, "lstm dg")]
     _timed(f"lstm_bwd[{N}x{T}x{H} bf{int(bool(bf16))}]", 4 * (ng + ns), 2 * N * T * 2 * 4 * H * H,
-           lambda: call("avd_lstm_bwd", p(dout), p(whh_f), p(whh_r), p(save), p(dg),
-                        BF16 if bf16 else F32, N, T, H, stream()))
+           lambda: call("avd_lstm_bwd", *a, BF16 if bf16 else F32, N, T, H, stream()))
 
 
 def cast(src, dst, n):
@@ -1238,15 +1212,11 @@ MHSA_TMAX = 256                    # tokens per sequence
 LN_EMAX = 512
 
 
-def _mmat(m, rows, E, what):
-    """A strided attention operand (tensor, element offset, ld): rows at off + r ld.  Checks that
-    everything the kernel may touch lies inside the tensor; returns (address, ld)."""
-    t, off, ld = m
-    _need(t.dtype == torch.float32 and t.is_contiguous(), f"mhsa {what}: contiguous f32")
-    _need(ld >= E and ld % 4 == 0 and off % 4 == 0 and off >= 0,
-          f"mhsa {what}: ld >= heads*dh, ld / offset multiples of 4")
-    _need(off + (rows - 1) * ld + E <= t.numel(), f"mhsa {what} bounds")
-    return t.data_ptr() + 4 * off, ld
+def _margs(ms, rows, E):
+    """The (address, ld) arguments of strided attention operands ((tensor, element offset, ld),
+    name): rows at off + r ld, all of which must lie inside the tensor."""
+    return [y for (t, off, ld), what in ms
+            for y in (_rows(t, off, ld, rows, E, f"mhsa {what}", align=4), ld)]
 
 
 def _mdims(N, heads, T, dh, drop_p):
@@ -1267,12 +1237,11 @@ def mhsa_fwd(q, k, v, ctx, lse, N, heads, T, dh, scale, bf16, drop_p=0.0, seed=0
     (tensor, element offset, ld); lse [N*heads*T] or None."""
     _mdims(N, heads, T, dh, drop_p)
     E, R = heads * dh, N * T
-    a = [_mmat(m, R, E, n) for m, n in ((q, "q"), (k, "k"), (v, "v"), (ctx, "ctx"))]
-    _need(lse is None or (lse.dtype == torch.float32 and lse.is_contiguous()
-                          and lse.numel() >= N * heads * T), "mhsa lse size")
+    a = _margs(((q, "q"), (k, "k"), (v, "v"), (ctx, "ctx")), R, E)
+    a.append(None if lse is None else _flat(lse, N * heads * T, "mhsa lse"))
     _timed(f"mhsa_fwd[{N}x{heads}x{T}x{dh} bf{int(bool(bf16))}]", 4 * 4 * R * E, 4 * N * heads * T * T * dh,
-           lambda: call("avd_mhsa_fwd", *[y for m in a for y in m], p(lse), N, heads, T, dh,
-                        BF16 if bf16 else F32, scale, drop_p, seed, _soff(seed_off), stream()))
+           lambda: call("avd_mhsa_fwd", *a, N, heads, T, dh, BF16 if bf16 else F32, scale, drop_p, seed,
+                        _soff(seed_off), stream()))
 
 
 def mhsa_bwd_ws(N, heads, T, dh):
@@ -1285,22 +1254,13 @@ def mhsa_bwd(dout, q, k, v, lse, dq, dk, dv, ws, N, heads, T, dh, scale, bf16, d
     """dQ, dK, dV from dctx, Q, K, V and the forward's lse (avd_mhsa_bwd)."""
     _mdims(N, heads, T, dh, drop_p)
     E, R = heads * dh, N * T
-    a = [_mmat(m, R, E, n) for m, n in ((dout, "dout"), (q, "q"), (k, "k"), (v, "v"))]
-    g = [_mmat(m, R, E, n) for m, n in ((dq, "dq"), (dk, "dk"), (dv, "dv"))]
-    _need(lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= N * heads * T,
-          "mhsa lse size")
-    _need(ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= mhsa_bwd_ws(N, heads, T, dh),
-          "mhsa workspace")
+    a = _margs(((dout, "dout"), (q, "q"), (k, "k"), (v, "v")), R, E)
+    g = _margs(((dq, "dq"), (dk, "dk"), (dv, "dv")), R, E)
+    a += [_flat(lse, N * heads * T, "mhsa lse"), *g,
+          _flat(ws, mhsa_bwd_ws(N, heads, T, dh), "mhsa workspace")]
     _timed(f"mhsa_bwd[{N}x{heads}x{T}x{dh} bf{int(bool(bf16))}]", 4 * 7 * R * E, 10 * N * heads * T * T * dh,
-           lambda: call("avd_mhsa_bwd", *[y for m in a for y in m], p(lse), *[y for m in g for y in m],
-                        p(ws), ws.numel(), N, heads, T, dh, BF16 if bf16 else F32, scale, drop_p, seed,
-                        _soff(seed_off), stream()))
-
-
-def _lrows(t, off, ld, rows, E, what):
-    _need(t.dtype == torch.float32 and t.is_contiguous() and ld >= E and off >= 0
-          and off + (rows - 1) * ld + E <= t.numel(), f"layer norm {what} bounds")
-    return t.data_ptr() + 4 * off
+           lambda: call("avd_mhsa_bwd", *a, ws.numel(), N, heads, T, dh, BF16 if bf16 else F32, scale,
+                        drop_p, seed, _soff(seed_off), stream()))
 
 
 def _ldims(rows, E):
@@ -1320,10 +1280,10 @@ def ln_fwd(x, res, gamma, beta, y, rows, E, z=None, mean=None, rstd=None, eps=1e
     _need(z is None or z.numel() >= rows * E, "layer norm z size")
     _need((mean is None or mean.numel() >= rows) and (rstd is None or rstd.numel() >= rows),
           "layer norm statistics size")
-    rp = None if res is None else _lrows(res, 0, res_ld, rows, E, "res")
-    call("avd_ln_fwd", _lrows(x, x_off, x_ld, rows, E, "x"), x_ld, rp, res_ld, p(gamma), p(beta),
-         _lrows(y, y_off, y_ld, rows, E, "y"), y_ld, p(z), p(mean), p(rstd), rows, E, eps, drop_p, seed,
-         _soff(seed_off), stream())
+    rp = None if res is None else _rows(res, 0, res_ld, rows, E, "layer norm res")
+    call("avd_ln_fwd", _rows(x, x_off, x_ld, rows, E, "layer norm x"), x_ld, rp, res_ld, p(gamma), p(beta),
+         _rows(y, y_off, y_ld, rows, E, "layer norm y"), y_ld, p(z), p(mean), p(rstd), rows, E, eps, drop_p,
+         seed, _soff(seed_off), stream())
 
 
 def ln_bwd_ws(rows, E):
@@ -1340,12 +1300,11 @@ def ln_bwd(dy, z, mean, rstd, gamma, dx, dr, dgamma, dbeta, ws, rows, E, drop_p=
     dr_ld = E if dr_ld is None else dr_ld
     _need(z.numel() >= rows * E and mean.numel() >= rows and rstd.numel() >= rows
           and gamma.numel() >= E and dgamma.numel() >= E and dbeta.numel() >= E, "layer norm sizes")
-    _need(ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= ln_bwd_ws(rows, E),
-          "layer norm workspace")
-    rp = None if dr is None else _lrows(dr, 0, dr_ld, rows, E, "dr")
-    call("avd_ln_bwd", _lrows(dy, dy_off, dy_ld, rows, E, "dy"), dy_ld, p(z), p(mean), p(rstd), p(gamma),
-         _lrows(dx, dx_off, dx_ld, rows, E, "dx"), dx_ld, rp, dr_ld, p(dgamma), p(dbeta), p(ws),
-         ws.numel(), rows, E, drop_p, seed, _soff(seed_off), stream())
+    wp = _flat(ws, ln_bwd_ws(rows, E), "layer norm workspace")
+    rp = None if dr is None else _rows(dr, 0, dr_ld, rows, E, "layer norm dr")
+    call("avd_ln_bwd", _rows(dy, dy_off, dy_ld, rows, E, "layer norm dy"), dy_ld, p(z), p(mean), p(rstd),
+         p(gamma), _rows(dx, dx_off, dx_ld, rows, E, "layer norm dx"), dx_ld, rp, dr_ld, p(dgamma), p(dbeta),
+         wp, ws.numel(), rows, E, drop_p, seed, _soff(seed_off), stream())
 
 
 def gelu_fwd(x, out, rows, C, drop_p=0.0, seed=0, seed_off=None):
