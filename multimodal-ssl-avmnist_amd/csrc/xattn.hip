@@ -14,8 +14,9 @@
 // as the B operand as is (V^T read with ds_read_b64_tr_b16).  Scores never reach HBM.
 //
 // avd_xattn_bwd recomputes P from the forward's row log-sum-exp:
-//   rows pass    (wave = 16 queries, streams keys, twice): delta_i = sum_j P_ij dP_ij with
-//                dP = dO V^T, then dS = P o (dP - delta), dQ = scale dS K
+//   rows pass    (wave = 16 queries, streams keys, twice): delta_i = sum_j P_ij dP_ij / sum_j P_ij
+//                with dP = dO V^T (kept relative to the dP of the row's largest P, see the
+//                kernel), then dS = P o (dP - delta), dQ = scale dS K
 //   columns pass (wave = 16 keys, streams queries): dV = P^T dO, dK = scale dS^T Q
 // A block owns its rows / columns outright: no split, no atomics, every sum in a fixed order.
 // The feature accumulators are cut in chunks of EC columns (grid z) to bound the registers; each
@@ -260,7 +261,12 @@ __global__ __launch_bounds__(XT) void xattn_bwd_rows_kernel(XaArgs a) {
   const size_t srow = ((size_t)d * a.groups + gi) * B + row;
   const float lse = row < B ? a.lse[srow] : INFINITY;        // rows past B: p = 0
   const int nblk = (B + XB - 1) / XB;
-  float delta = 0.f;
+  // delta = sum_j P dP / sum_j P is kept as c + dc around c = the dP of the row's largest P:
+  // P recomputed from an f32 lse sums to 1 only within |lse| 2^-24, and in a row whose softmax is
+  // nearly one-hot dP_top - delta is ~(1 - P_top) |dP|, far below what an f32 sum_j P dP resolves.
+  // With dc = sum_j P (dP - c) / sum_j P the top key's own term is exactly zero, so
+  // dS = P ((dP - c) - dc) keeps its relative accuracy however small it is.
+  float c = 0.f, pm = -1.f, sp = 0.f, dcs = 0.f, dc = 0.f;
   f4 acc[EC / 16];
 #pragma unroll
   for (int t = 0; t < EC / 16; ++t) acc[t] = f4{0.f, 0.f, 0.f, 0.f};
@@ -272,25 +278,56 @@ __global__ __launch_bounds__(XT) void xattn_bwd_rows_kernel(XaArgs a) {
       f4 st[2], dp[2];
       scores<E>(kb, oq, lane, st);
       scores<E>(vb, od, lane, dp);
-      float ds[8], part = 0.f;
+      float p[8];
 #pragma unroll
       for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int j = b * XB + 16 * h + 4 * g + e;
-          const float p = j < B ? __expf(st[h][e] * a.scale - lse) : 0.f;
-          part += p * dp[h][e];
-          ds[4 * h + e] = p * (dp[h][e] - delta);
+          p[4 * h + e] = j < B ? __expf(st[h][e] * a.scale - lse) : 0.f;
         }
       if (pass == 0) {
+        // the block's largest P of this row and its dP: over the lane's 8 keys, then the 4 lanes
+        // of the row (larger P, then larger dP: every lane of the row ends with the same pair)
+        float bp = -1.f, bc = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float dv = dp[e >> 2][e & 3];
+          if (p[e] > bp || (p[e] == bp && dv > bc)) { bp = p[e]; bc = dv; }
+        }
+#pragma unroll
+        for (int m = 16; m <= 32; m <<= 1) {
+          const float op = __shfl_xor(bp, m, 64), oc = __shfl_xor(bc, m, 64);
+          if (op > bp || (op == bp && oc > bc)) { bp = op; bc = oc; }
+        }
+        if (bp > pm) {                          // a new reference: sum P (dP - c) moves with it
+          dcs += (c - bc) * sp;
+          c = bc;
+          pm = bp;
+        }
+        float part = 0.f, ps = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          part += p[e] * (dp[e >> 2][e & 3] - c);
+          ps += p[e];
+        }
         part += __shfl_xor(part, 16, 64);
         part += __shfl_xor(part, 32, 64);
-        delta += part;                          // running until the pass ends; ds unused here
+        ps += __shfl_xor(ps, 16, 64);
+        ps += __shfl_xor(ps, 32, 64);
+        dcs += part;
+        sp += ps;
       } else {
+        float ds[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ds[e] = p[e] * ((dp[e >> 2][e & 3] - c) - dc);
         accum<E, EC / 16>(kb, pack8(ds), lane, t0, acc);
       }
     }
-    if (pass == 0 && blockIdx.z == 0 && g == 0 && row < B) a.delta[srow] = delta;
+    if (pass == 0) {
+      dc = sp > 0.f ? dcs / sp : 0.f;           // rows past B: every P is zero
+      if (blockIdx.z == 0 && g == 0 && row < B) a.delta[srow] = c + dc;
+    }
   }
   if (row < B) {
     float* o = a.dq + (size_t)d * a.dsdq + ((size_t)gi * B + row) * a.lddq;

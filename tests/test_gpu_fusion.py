@@ -154,7 +154,10 @@ def _attn64(q, k, v, x, do, scale, rounded):
     return x + pr @ v, scale * dsr @ k, scale * dsr.transpose(1, 2) @ q, pr.transpose(1, 2) @ do
 
 
-@pytest.mark.parametrize("E,B", [(32, 5), (128, 70)])
+FUSED_ROUTE_CASES = [(32, 5), (128, 70), (256, 70), (64, 17)]     # (256, 70): the configured size
+
+
+@pytest.mark.parametrize("E,B", FUSED_ROUTE_CASES)
 def test_bf16_fused_route_matches_plain_route(E, B):
     """One engine, one state: the mix stage forward and backward by the fused kernel and by the
     plain route, from the same cat and the same gradient of fusion's input."""

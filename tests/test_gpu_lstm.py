@@ -2,11 +2,21 @@
 them -- engine.lstm_forward / lstm_backward, from token rows to the mean-over-time output and to
 every gradient -- against torch.nn.LSTM in float64 on the CPU followed by the mean.
 
-Shapes, the smallest that can break it: T in {1, 2, 3, 196}; H in {16 (K padded to the bf16
-MFMA's 32), 48 (not a power of two, three of the four waves busy), 128 (two unit tiles per wave,
-the full-residency case)}; N in {1, 15, 17, 35} around the kernel's 16-sequence block.  Every
-(T, H) pair runs, with N cycling so that every N meets every T and H at least once.  Inputs are
-random, so asymmetric in time; both biases are non-zero and different.
+Shapes, the smallest that can break it: T in {1, 2, 3, 49 (the multi_lstm image tower), 196 (the
+audio tower)}; H every size the dispatcher instantiates (ops.LSTM_HIDDEN).  A wave owns the unit
+tiles u = wave, wave + 4 of the NU = H / 16; the bf16 MFMA pads the forward's K = H to a multiple
+of 32:
+  H = 16   NU 1: wave 0 alone, three waves idle; K padded 16 -> 32
+  H = 32   NU 2: waves 2 and 3 idle; no padding
+  H = 48   NU 3: wave 3 idle (not a power of two); K padded 48 -> 64
+  H = 64   NU 4: exactly one tile per wave; no padding
+  H = 80   NU 5: only wave 0 has a second tile; K padded 80 -> 96
+  H = 96   NU 6: waves 0 and 1 have a second tile; no padding
+  H = 112  NU 7: wave 3 alone has no second tile; K padded 112 -> 128
+  H = 128  NU 8: two tiles per wave, the full-residency case; no padding
+N in {1, 15, 17, 35} around the kernel's 16-sequence block.  Every (T, H) pair runs, with N cycling
+so that every N meets every T and H at least once.  Inputs are random, so asymmetric in time; both
+biases are non-zero and different.
 
 f32 band: rel-L2 per tensor <= max(1e-5, 3 x the error of torch's own float32 CPU nn.LSTM against
 the same float64 run) -- two independent roundings of the same size.
@@ -23,17 +33,26 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+from avdino import ops  # noqa: E402
+
 I = 64
-TS, HS, NS = (1, 2, 3, 196), (16, 48, 128), (1, 15, 17, 35)
-CASES = [(T, H, NS[(i + j) % 4]) for i, T in enumerate(TS) for j, H in enumerate(HS)]
+TS, HS, NS = (1, 2, 3, 49, 196), ops.LSTM_HIDDEN, (1, 15, 17, 35)
+# N cycles over (T, H) in the order the sizes joined the table, so the earlier cases keep their N
+_T_ORDER = (1, 2, 3, 196) + tuple(T for T in TS if T not in (1, 2, 3, 196))
+_H_ORDER = (16, 48, 128) + tuple(H for H in HS if H not in (16, 48, 128))
+CASES = [(T, H, NS[(_T_ORDER.index(T) + _H_ORDER.index(H)) % 4]) for T in TS for H in HS]
 NAMES = [n + s for s in ("", "_reverse")
          for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
 
 
 def test_case_table_covers_every_size():
+    assert set(HS) == set(ops.LSTM_HIDDEN) and len(HS) == 8
     assert {c[0] for c in CASES} == set(TS) and {c[1] for c in CASES} == set(HS)
-    assert {c[2] for c in CASES} == set(NS) and len({c[:2] for c in CASES}) == 12
-    from avdino import ops
+    assert {c[2] for c in CASES} == set(NS)
+    assert {c[:2] for c in CASES} == {(T, H) for T in TS for H in HS} and len(CASES) == 40
+    for N in NS:                                      # every N meets every T and every H
+        assert {c[0] for c in CASES if c[2] == N} == set(TS), N
+        assert {c[1] for c in CASES if c[2] == N} == set(HS), N
     assert ops.LSTM_BLOCK == 16 and NS == (1, ops.LSTM_BLOCK - 1, ops.LSTM_BLOCK + 1, 2 * ops.LSTM_BLOCK + 3)
 
 
@@ -186,7 +205,7 @@ def test_bf16_within_three_times_the_restated_rounding(T, H, N):
 
 
 @pytest.mark.parametrize("bf16", [False, True])
-@pytest.mark.parametrize("T,H,N", [(3, 48, 35), (196, 128, 17), (2, 16, 1)])
+@pytest.mark.parametrize("T,H,N", [(3, 48, 35), (196, 128, 17), (2, 16, 1), (49, 80, 17), (3, 112, 35)])
 def test_runs_are_bitwise_reproducible(T, H, N, bf16):
     (x, prm, dout), _, _, _ = reference(T, H, N)
     a, ws = gpu_lstm(x, prm, dout, H, bf16)
@@ -197,7 +216,7 @@ def test_runs_are_bitwise_reproducible(T, H, N, bf16):
 
 
 @pytest.mark.parametrize("bf16", [False, True])
-@pytest.mark.parametrize("T,H,N", [(3, 48, 35), (196, 128, 17)])
+@pytest.mark.parametrize("T,H,N", [(3, 48, 35), (196, 128, 17), (49, 80, 17), (3, 112, 35)])
 def test_no_save_is_bitwise_the_same_and_leaves_the_buffer_alone(T, H, N, bf16):
     from avdino import ops
     (x, prm, dout), _, _, _ = reference(T, H, N)

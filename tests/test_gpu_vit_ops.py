@@ -5,6 +5,13 @@ Attention tiling named for the shapes below: a workgroup owns 16 rows of one (se
 queries in the forward and the backward's row pass, keys in its column pass -- against all T keys
 (queries), one per thread.  T = 197 = 12 * 16 + 5 is the audio ViT's own ragged case, T = 16 / 17
 sit on and next to the tile edge, T = 50 is the image ViT's length, T = 1 / 5 are below one tile.
+T = 256 = ops.MHSA_TMAX is the one length at which every thread holds a row and every 16-row tile
+is full, 255 its ragged neighbour.  dh runs over ops.MHSA_HEAD_DIMS: each head size is its own
+six kernels (forward, row pass, column pass, f32 and bf16).
+
+LayerNorm: a lane holds elements l + 64 k; E = 96 leaves the middle chunk half valid, E = 480 the
+last one; rows = 32800 is past the backward's 1024-block cap (trailing blocks own no row).  GELU:
+8193 x 2048 elements is past 65536 blocks x 256 threads, so the grid-stride loop wraps.
 
 f32 mode: rel-L2 < 1e-5 on ctx, lse, dQ, dK, dV (the band the engine's outputs take).
 bf16 mode (computed, per output tensor, rel-L2): the same formulas in float64 with Q, K, V, dO
@@ -18,6 +25,7 @@ import numpy as np
 import pytest
 import torch
 
+from avdino import ops
 from tests import vit_ref as VR
 
 pytestmark = pytest.mark.gpu
@@ -25,6 +33,13 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SENT = 777.0
 TILE = 16
+MHSA_DHS = ops.MHSA_HEAD_DIMS                     # every dispatched head size
+MHSA_TS = (1, 5, 16, 17, 50, 197, 255, 256)
+MHSA_DROPOUT_CASES = [(3, 4, 17, 32, 0.1), (3, 4, 197, 32, 0.1), (3, 4, 197, 128, 0.5), (1, 1, 50, 128, 0.1),
+                      (3, 4, 256, 64, 0.1)]
+LN_ES = (32, 96, 480, 512)
+LN_CAP_ROWS, LN_CAP_E = 32 * 1024 + 32, 32        # rows past the backward's block cap
+GELU_WRAP = (8193, 2048)                          # 16 779 264 elements: just past 65536 x 256
 
 
 def bf(t):
@@ -95,7 +110,6 @@ def run_kernel(q, k, v, do, scale, bf16, p=0.0, seed=0, seed_off=None, with_lse=
     """Q / K / V as the column slices of a [rows + 1, 3E] buffer (one guard row), ctx and dctx as
     halves of [rows + 2, 2E] buffers, the gradients as slices of a [rows + 1, 4E] buffer; everything
     else sentinel."""
-    from avdino import ops
     N, heads, T, dh = q.shape
     E, rows = heads * dh, N * T
     qkv = torch.full((rows + 1, 3 * E), SENT)
@@ -162,16 +176,15 @@ def check_case(N, heads, T, dh, bf16, p=0.0, seed=0, std=8.0):
 
 
 @pytest.mark.parametrize("bf16", [False, True])
-@pytest.mark.parametrize("dh", [32, 128])
-@pytest.mark.parametrize("T", [1, 5, 16, 17, 50, 197])
+@pytest.mark.parametrize("dh", MHSA_DHS)
+@pytest.mark.parametrize("T", MHSA_TS)
 @pytest.mark.parametrize("N,heads", [(1, 1), (3, 1), (1, 4), (3, 4)])
 def test_mhsa_matches_float64(N, heads, T, dh, bf16):
     check_case(N, heads, T, dh, bf16)
 
 
 @pytest.mark.parametrize("bf16", [False, True])
-@pytest.mark.parametrize("N,heads,T,dh,p", [(3, 4, 17, 32, 0.1), (3, 4, 197, 32, 0.1), (3, 4, 197, 128, 0.5),
-                                           (1, 1, 50, 128, 0.1)])
+@pytest.mark.parametrize("N,heads,T,dh,p", MHSA_DROPOUT_CASES)
 def test_mhsa_dropout_matches_float64_with_the_numpy_mask(N, heads, T, dh, p, bf16):
     mask = check_case(N, heads, T, dh, bf16, p=p, seed=(1 << 50) + 977)
     if mask.numel() >= 131072:
@@ -195,7 +208,6 @@ def test_mhsa_milder_logits_and_the_device_seed_offset():
 
 
 def test_mhsa_rejects_bad_shapes_and_strides_without_a_launch():
-    from avdino import ops
     N, heads, T, dh = 2, 2, 5, 32
     E, R = heads * dh, N * T
     qkv = torch.full((R, 3 * E), SENT, device=DEV)
@@ -231,12 +243,10 @@ def ln_reference(x, r, mask, gamma, beta, dy, eps=1e-5):
     return y.detach(), x.grad, None if r is None else r.grad, gamma.grad, beta.grad
 
 
-@pytest.mark.parametrize("with_r,pad,p", [(False, 0, 0.0), (True, 0, 0.0), (True, 24, 0.0), (False, 24, 0.0),
-                                          (True, 0, 0.1), (True, 24, 0.1)])     # dropout: on the branch
-@pytest.mark.parametrize("E", [32, 512])
-@pytest.mark.parametrize("rows", [1, 7, 300])
-def test_layer_norm_matches_float64(rows, E, with_r, pad, p):
-    from avdino import ops
+def check_layer_norm(rows, E, with_r, pad, p, poison_ws=False):
+    """ln_fwd / ln_bwd against float64: y, dx, dr, dgamma, dbeta, the pad columns, the constant
+    row, bit-reproducibility.  poison_ws: the backward's workspace is all NaN before each call, so
+    a block that skips its partial write shows in dgamma and dbeta."""
     g = torch.Generator().manual_seed(rows * 1000 + E + pad)
     x = torch.randn(rows, E, generator=g) * 2.0 + 0.5
     r = torch.randn(rows, E, generator=g) if with_r else None
@@ -275,6 +285,8 @@ def test_layer_norm_matches_float64(rows, E, with_r, pad, p):
     runs = []
     for _ in range(2):
         dg, db = torch.empty(E, device=DEV), torch.empty(E, device=DEV)
+        if poison_ws:
+            ws.fill_(float("nan"))
         ops.ln_bwd(dyd, z, mean, rstd, gd, dx, dr, dg, db, ws, rows, E, p, seed, None, dy_ld=ld, dx_ld=ld, dr_ld=ld)
         runs.append((dx.cpu().clone(), dg.cpu(), db.cpu()) + ((dr.cpu().clone(),) if with_r else ()))
     assert all(torch.equal(a, b) for a, b in zip(*runs)), "layer norm gradients not bit-reproducible"
@@ -293,10 +305,28 @@ def test_layer_norm_matches_float64(rows, E, with_r, pad, p):
         assert v < (1e-5 if k in ("dgamma", "dbeta") else 1e-6), (k, v)
 
 
+@pytest.mark.parametrize("with_r,pad,p", [(False, 0, 0.0), (True, 0, 0.0), (True, 24, 0.0), (False, 24, 0.0),
+                                          (True, 0, 0.1), (True, 24, 0.1)])     # dropout: on the branch
+@pytest.mark.parametrize("E", LN_ES)
+@pytest.mark.parametrize("rows", [1, 7, 300])
+def test_layer_norm_matches_float64(rows, E, with_r, pad, p):
+    check_layer_norm(rows, E, with_r, pad, p)
+
+
+@pytest.mark.parametrize("with_r,p", [(False, 0.0), (True, 0.1)])
+def test_layer_norm_past_the_backward_block_cap(with_r, p):
+    """More than 32 x 1024 rows: the backward's grid is capped, a block walks rpb = 33 rows and
+    the blocks from 994 on own none -- they must still write zero partials."""
+    rows, E = LN_CAP_ROWS, LN_CAP_E
+    blocks = ops.ln_bwd_ws(rows, E) // (2 * E)
+    rpb = -(-rows // blocks)
+    assert blocks == 1024 and rpb == 33 and 993 * rpb < rows <= 994 * rpb
+    check_layer_norm(rows, E, with_r, 0, p, poison_ws=True)
+
+
 def test_final_norm_on_the_cls_rows_with_a_token_stride():
     """The tower's last LayerNorm: rows T*E apart in, dense out; the backward writes the cls rows of
     a [N, T, E] gradient and nothing else."""
-    from avdino import ops
     N, T, E = 3, 5, 64
     g = torch.Generator().manual_seed(3)
     h = torch.randn(N, T, E, generator=g)
@@ -319,7 +349,6 @@ def test_final_norm_on_the_cls_rows_with_a_token_stride():
 @pytest.mark.parametrize("p", [0.0, 0.1])
 @pytest.mark.parametrize("rows,C", [(1, 1), (7, 33), (300, 2048)])
 def test_gelu_matches_float64(rows, C, p):
-    from avdino import ops
     g = torch.Generator().manual_seed(rows + C)
     x = torch.randn(rows, C, generator=g) * 2.0
     do = torch.randn(rows, C, generator=g)
@@ -342,10 +371,42 @@ def test_gelu_matches_float64(rows, C, p):
         assert bool((oh[m == 0] == 0).all()) and bool((oh[(m > 0) & (x.abs() > 1e-3) & (x.abs() < 4)] != 0).all())
 
 
+@pytest.mark.parametrize("p", [0.0, 0.1])
+def test_gelu_past_the_grid_cap(p):
+    """More elements than 65536 blocks x 256 threads: the grid-stride loop takes a second trip for
+    the elements from 16 777 216 on (the audio ViT's MLP activation is there from N = 42)."""
+    rows, C = GELU_WRAP
+    n, wrap = rows * C, 65536 * 256
+    assert n > wrap
+    g = torch.Generator().manual_seed(rows + C)
+    x = torch.randn(n, generator=g) * 2.0
+    do = torch.randn(n, generator=g)
+    seed = 99
+    m = torch.from_numpy(VR.dropout_scale(seed, np.arange(n, dtype=np.uint64), p))
+    x64 = x.double()
+    cdf = 0.5 * (1.0 + torch.erf(x64 / math.sqrt(2.0)))
+    out = x64 * cdf * m
+    dx64 = do.double() * m * (cdf + x64 * torch.exp(-0.5 * x64 * x64) / math.sqrt(2.0 * math.pi))
+    xd, o, dx = x.to(DEV), torch.empty(n + 1, device=DEV), torch.empty(n + 1, device=DEV)
+    o[-1], dx[-1] = SENT, SENT
+    ops.gelu_fwd(xd, o, rows, C, p, seed)
+    ops.gelu_bwd(xd, do.to(DEV), dx, rows, C, p, seed)
+    assert float(o[-1]) == SENT and float(dx[-1]) == SENT
+    oh, dh = o[:-1].cpu(), dx[:-1].cpu()
+    eo, ed = rel(oh.double(), out), rel(dh.double(), dx64)
+    ew, edw = rel(oh[wrap:].double(), out[wrap:]), rel(dh[wrap:].double(), dx64[wrap:])
+    print(f"gelu {rows}x{C} p{p}: out {eo:.2e} dx {ed:.2e}; wrapped part out {ew:.2e} dx {edw:.2e}")
+    assert eo < 1e-6 and ed < 1e-6 and ew < 1e-6 and edw < 1e-6
+    if p > 0:
+        mw, xw = m[wrap:], x[wrap:]
+        assert 0 < int((mw == 0).sum()) < mw.numel()
+        assert bool((oh[wrap:][mw == 0] == 0).all()) and bool((dh[wrap:][mw == 0] == 0).all())
+        assert bool((oh[wrap:][(mw > 0) & (xw.abs() > 1e-3) & (xw.abs() < 4)] != 0).all())
+
+
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("N,H,P", [(1, 16, 8), (3, 16, 8), (1, 112, 8), (3, 112, 8)])
 def test_patchify_is_exact(N, H, P, dt):
-    from avdino import ops
     g = torch.Generator().manual_seed(N + H)
     x = torch.rand(N, 1, H, H, generator=g).to(dt)
     want = VR.patch_rows(x.float(), P).reshape(-1, P * P)
@@ -361,7 +422,6 @@ def test_patchify_is_exact(N, H, P, dt):
 
 @pytest.mark.parametrize("N,T,E", [(1, 5, 32), (3, 5, 32), (3, 197, 512)])
 def test_tokens_forward_and_backward(N, T, E):
-    from avdino import ops
     g = torch.Generator().manual_seed(N + T)
     pe, cls, pos = torch.randn(N, T - 1, E, generator=g), torch.randn(E, generator=g), torch.randn(T, E, generator=g)
     want = torch.cat([cls.expand(N, 1, E), pe], 1) + pos
