@@ -176,6 +176,12 @@ int avd_linear_bwd_hwc(int rows, int O, int C, int HW, const float* dout, long l
  * conv -> BatchNorm2d(train) -> ReLU -> max_pool2d(2) block of CentralUnimodalImage /
  * CentralUnimodalAudio.forward (unimodal.py:127-221) and the 3x3 CNN blocks (dino.py:18-73),
  * forward and backward.  K in {3, 5}; Cin = 1 or a multiple of 8; Cout a multiple of 8.
+ * The generic forward and input-gradient kernels are instantiated per channel count of the map
+ * they READ -- x in avd_cl_conv_fwd, dy in avd_cl_conv_dgrad: 8, 16, 32, 64 and, for 3x3, 128 and
+ * 256 (the forward also 1).  Any other multiple of 8 there (24, 40, 72, 96 ...) is AVD_ERR_SHAPE
+ * before any launch; the map they WRITE takes any multiple of 8 (a ragged last 16-channel MFMA
+ * tile: Cout 24, 40, 72 forward, Cin 24, 40, 72 in the input gradient), and so do both operands of
+ * avd_cl_conv_wgrad (Cin = 1: Cout <= 64).  tests/test_gpu_conv_exact.py pins which.
  * H and W are independent everywhere below: a rectangular map is either served (same results as
  * the square-map contract) or declined -- the sizing query answers 0 or the entry point returns
  * AVD_ERR_SHAPE before any launch (tests/test_gpu_rect.py pins which).  The routes measured for

@@ -379,7 +379,12 @@ __global__ __launch_bounds__(512, 1) void conv3p_kernel(
 
 struct Plan3 { int TR, NS, GPW, tilesPS, IW8, xrows; };
 
-int iw8_of(int W) { return (W + 2 + XPAD - 1) / XPAD * XPAD; }
+// padded input row (pixels) of a W-wide map: W + 2 rounded up to the instantiated strides 16, 32,
+// 64 (a 48-pixel row, W = 31..46, runs on the 64-pixel kernels: the columns past W + 1 are zero)
+int iw8_of(int W) {
+  const int p = (W + 2 + XPAD - 1) / XPAD * XPAD;
+  return p == 48 ? 64 : p;
+}
 
 // The tile with the best utilisation of GPW*64 pixel slots (ties: more pixels); whole small
 // maps are packed NS per block with NS | B (a tile never straddles two BatchNorm groups); the

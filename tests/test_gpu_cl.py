@@ -4,7 +4,9 @@ against the float64 numpy oracle, in both storage types:
   bf16 (v_mfma_f32_16x16x32_bf16 on bf16-rounded operands, fp32 accumulate, bf16 stores):
        rel-L2 <= 5e-3 on stored maps (one bf16 rounding), 1e-5 on f32 reductions of them.
 Shapes cover every conv of the CentralNet image/audio encoders and the 3x3 CNNs, ragged
-tilings, whole-map packing of small maps (NS > 1), and two BN groups."""
+tilings, whole-map packing of small maps (NS > 1), and two BN groups.
+A whole-tensor norm cannot see a few wrong elements: localised errors are caught bit for bit by
+tests/test_gpu_conv_exact.py."""
 import numpy as np
 import pytest
 

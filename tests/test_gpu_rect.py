@@ -9,6 +9,8 @@ square test of the same entry point asserts it, bit for bit with the unfused lau
 tolerances of that square test:
   tests/test_gpu_cl.py: stored maps rel-L2 2e-6 (f32) / 5e-3 (bf16), f32 reductions 1e-5;
   torch.equal wherever a fused route is defined as bit-identical to the launches it replaces.
+(Those norms cannot see a few wrong elements: localised errors are caught bit for bit by
+tests/test_gpu_conv_exact.py, rectangular maps included.)
 A zero row count or AVD_ERR_SHAPE on a "served" row fails; a "declined" row must answer 0 from its
 sizing query, and where the host check stands before the first launch the entry point itself is
 called and must return AVD_ERR_SHAPE with its sentinel-filled outputs untouched.
