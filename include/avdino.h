@@ -384,6 +384,7 @@ int avd_cast(const void* src, int src_dt, void* dst, int dst_dt, long long n, vo
  * dt = AVD_F32: exact f32 fma chains (the parity yardstick).  dt = AVD_BF16: Q, K, V and the
  * dropped-out probabilities are rounded to bf16 (the operands of the two products), f32
  * accumulation -- on the VALU in this version, not yet on the MFMA.
+ * avd_mhsa_mfma_fwd / _bwd below are the bf16 mode on the MFMA.
  * dh in {32, 64, 128}, heads >= 1, 1 <= T <= 256, 1 <= N <= 65535, else AVD_ERR_SHAPE; pointers
  * 16-byte aligned, leading dimensions >= heads*dh and multiples of 4 floats, else AVD_ERR_ARG;
  * dt other than the two: AVD_ERR_DTYPE. */
@@ -409,6 +410,32 @@ int avd_mhsa_bwd(const float* dout, long long lddo, const float* q, long long ld
                  long long lddq, float* dk, long long lddk, float* dv, long long lddv, float* ws,
                  long long ws_elems, int N, int heads, int T, int dh, int dt, float scale, float p,
                  unsigned long long seed, const unsigned long long* seed_off, void* stream);
+
+/* The same attention on the bf16 MFMA (mhsa_mfma.hip): the contract of avd_mhsa_fwd / avd_mhsa_bwd
+ * at dt = AVD_BF16, without the dt argument (there is no f32 mode).  Operands, strides, lse
+ * ([N][heads][T], nullable, ctx bit-identical without it), the dropout key, hash and mask (at the
+ * same (seed, seed_off, p) the mask avd_mhsa_* draws; p = 0 evaluates no hash), shapes, alignment
+ * and return codes are those of avd_mhsa_*; a bad argument launches nothing.
+ * Flash form: a workgroup owns 64 query rows (a wave 16) and streams the keys in 32-key blocks
+ * staged as bf16 in LDS, online max / sum per query.  Rounded to bf16: Q, K, V, dO, the
+ * unnormalised masked probabilities exp(s - m) o M that enter P V (the row sum is that of the
+ * unmasked f32 values and divides the f32 accumulator at the end), and in the backward
+ * P o M = exp(s - lse) o M and dS.  dP = (dO V^T) o M; delta = sum_j P dP / sum_j P is kept in f32
+ * relative to the dP of the row's largest P, whose own term is then exactly zero, so dP - delta
+ * keeps its relative accuracy in a nearly one-hot row.  Rows pass (dQ, delta into ws) then
+ * columns pass (dK, dV); no T x T array in HBM, no atomics, every sum in a fixed order: two runs
+ * are bit-identical.  Keys past T are excluded from max and sum; nothing outside the owned rows
+ * and columns is written.  ws: avd_mhsa_mfma_bwd_ws(...) floats (-1: unsupported shape). */
+int avd_mhsa_mfma_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v,
+                      long long ldv, float* ctx, long long ldo, float* lse, int N, int heads, int T, int dh,
+                      float scale, float p, unsigned long long seed, const unsigned long long* seed_off,
+                      void* stream);
+long long avd_mhsa_mfma_bwd_ws(int N, int heads, int T, int dh);
+int avd_mhsa_mfma_bwd(const float* dout, long long lddo, const float* q, long long ldq, const float* k,
+                      long long ldk, const float* v, long long ldv, const float* lse, float* dq,
+                      long long lddq, float* dk, long long lddk, float* dv, long long lddv, float* ws,
+                      long long ws_elems, int N, int heads, int T, int dh, float scale, float p,
+                      unsigned long long seed, const unsigned long long* seed_off, void* stream);
 
 /* y[r] = LayerNorm(x[r] + dropout(res[r])) * gamma + beta over rows of E features (biased
  * variance, eps inside the square root: nn.LayerNorm); res nullable = plain LayerNorm (p is then

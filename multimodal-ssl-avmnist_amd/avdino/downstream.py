@@ -70,9 +70,12 @@ def _source(pretrained_model, is_dino_based=True):
 
 def _probe_kwargs(pretrained_model, is_dino_based):
     """LinearProbe's encoder selection for ``_source``'s model: the key prefix of a SimCLR tower,
-    or the two towers (image first, as the reference concatenates) of a late-fusion encoder."""
+    or the two towers (image first, as the reference concatenates) of a late-fusion encoder; for
+    a DINO model whose encoder spec chose its ViT attention kernels, that choice."""
     if is_dino_based:
-        return {}
+        m = pretrained_model.model if hasattr(pretrained_model, "configure_optimizers") else pretrained_model
+        attention = getattr(m.student_spec, "attention", "exact")
+        return {} if attention == "exact" else {"vit_attention": attention}
     enc = pretrained_model
     if hasattr(enc, "fusion"):
         return {"towers": [(enc.image_encoder.kind, enc.image_encoder.prefix),

@@ -26,7 +26,7 @@ from . import contrastive, ops
 from .capture import GraphedStep, host_point, new_event  # noqa: F401  (GraphedStep re-exported)
 from .spec import (HEAD_NAMES, LSTM_PROJ, MIX_KIND, MULTI_ENCODERS, PROJ_HIDDEN, UNI_ALIASES,
                    UNI_ENCODERS, VIT_ENCODERS, XATTN_NAMES, lstm_hidden)
-from .vit import ViTTower
+from .vit import ATTENTION_KINDS, ViTTower
 
 F32 = torch.float32
 # early gradient buckets at a host point inside the step (False: one all-reduce after the step)
@@ -1770,17 +1770,24 @@ class UniEncoder:
     SpectrogramEncoderViT (532-546; a spec.VIT_ENCODERS kind): no conv stack -- the staged map goes
     through a ViTTower (avdino/vit.py), then Linear(512, D) on its cls rows.
     ``drop`` = (p, base seed, seed_off, role) switches the tower's dropout on (vit.py; the other
-    kinds have none and ignore it)."""
+    kinds have none and ignore it).  ``vit_attention`` (vit.ATTENTION_KINDS) picks the tower's
+    attention kernels; a kind without a tower accepts only the default."""
 
-    def __init__(self, kind, prefix, act_dtype, gemm_mode, out_dim=None):
+    def __init__(self, kind, prefix, act_dtype, gemm_mode, out_dim=None, vit_attention="exact"):
         kind = UNI_ALIASES.get(kind, kind)
         self.vit = kind in VIT_ENCODERS
         self.gm = gemm_mode
+        if vit_attention not in ATTENTION_KINDS:
+            raise ValueError(f"vit_attention must be one of {ATTENTION_KINDS} (got {vit_attention!r})")
+        if vit_attention != "exact" and not self.vit:
+            raise ValueError(f"vit_attention={vit_attention!r}: encoder {kind!r} has no ViT tower")
+        self.vit_attention = vit_attention
         if self.vit:
             modality, tprefix, dims, lins, _sd = VIT_ENCODERS[kind]
             self.modality, self.lstm, self.branch = modality, False, None
             self.hw = dims["hw"]
-            self.tower = ViTTower(f"{prefix}.{tprefix}", act_dtype=act_dtype, gemm_mode=gemm_mode, **dims)
+            self.tower = ViTTower(f"{prefix}.{tprefix}", act_dtype=act_dtype, gemm_mode=gemm_mode,
+                                  attention=vit_attention, **dims)
             self.lins = [f"{prefix}.{k}" for k in lins]
             return
         modality, stack, lins, _sd = UNI_ENCODERS[kind]
@@ -1895,8 +1902,9 @@ class UniModalEngine:
     teacher EMA (before backward, dino.py:1661), backward, Adam with L2 weight decay."""
 
     def __init__(self, store, kind, D, P, hp, act_dtype=F32, cos_alpha=0.0, grad_hook=None,
-                 buffer_hook=None, seed=0, step_order="lightning"):
-        """step_order "lightning": UniModalDINOLightning.training_step + Adam(L2) (EMA before
+                 buffer_hook=None, seed=0, step_order="lightning", vit_attention="exact"):
+        """vit_attention: the attention kernels of a ViT encoder's two towers (vit.ATTENTION_KINDS).
+        step_order "lightning": UniModalDINOLightning.training_step + Adam(L2) (EMA before
         backward); "pretrain": training_structures.pretrain_dino (dino_train.py:137-166):
         AdamW (weight_decay 0.01) and the EMA AFTER the optimizer step, loss = the unimodal
         DINO loss only."""
@@ -1913,8 +1921,8 @@ class UniModalEngine:
         self.gm = ops.GEMM_BF16_MFMA if act_dtype == torch.bfloat16 else ops.GEMM_F32_MFMA
         self.cos_alpha = float(cos_alpha)
         self.ws = Workspace(store.device)
-        self.enc = UniEncoder(self.kind, "student", act_dtype, self.gm, out_dim=D)
-        self.t_enc = UniEncoder(self.kind, "teacher", act_dtype, self.gm, out_dim=D)
+        self.enc = UniEncoder(self.kind, "student", act_dtype, self.gm, out_dim=D, vit_attention=vit_attention)
+        self.t_enc = UniEncoder(self.kind, "teacher", act_dtype, self.gm, out_dim=D, vit_attention=vit_attention)
         self.modality = self.enc.modality
         self.sproj = ProjHead("student_projection", D, P, gemm_mode=self.gm)
         self.tproj = ProjHead("teacher_projection", D, P, gemm_mode=self.gm)

@@ -43,6 +43,7 @@ from . import contrastive, ops
 from .engine import Hyper, MultiCentralEngine, SimCLREngine, UniModalEngine, Workspace, ema_step
 from .params import ParamStore
 from .spec import LSTM_DIMS, MULTI_ENCODERS, multimodal_dino_sd, simclr_sd, unimodal_dino_sd
+from .vit import ATTENTION_KINDS
 
 try:  # a real drop-in under Lightning's Trainer where Lightning is installed
     from lightning.pytorch import LightningModule as _LightningBase
@@ -181,8 +182,18 @@ class SpectrogramEncoderViT(SpectrogramEncoder):
     """Sequential(AudioViTEncoder(112, patch 8, embed_dim 512, depth 4, heads 4), Linear(512,
     output_dim)) (models/dino.py:532-546; models/dino_vit.py:122-177): 196 patch tokens + cls,
     four post-norm transformer layers, the final LayerNorm's cls row.  Descriptor: the tower is
-    avdino/vit.py ViTTower on csrc/vit.hip."""
+    avdino/vit.py ViTTower on csrc/vit.hip.  ``attention`` (vit.ATTENTION_KINDS)
+    picks the tower's attention kernels: "exact" (avd_mhsa_*) or, bf16 only, "mfma"
+    (avd_mhsa_mfma_*).  It travels in ``encoder_kwargs``, so a checkpoint keeps it; one written
+    without it is "exact"."""
     kind = "spectrogram_vit"
+
+    def __init__(self, output_dim=256, attention="exact"):
+        if attention not in ATTENTION_KINDS:
+            raise ValueError(f"SpectrogramEncoderViT: attention must be one of {ATTENTION_KINDS} "
+                             f"(got {attention!r})")
+        super().__init__(output_dim)
+        self.attention = attention
 
 
 MODEL_MAP = {"multi_simple": SimpleMultiModalEncoder, "multi_simple_gated": GatedMultiModalEncoder,
@@ -881,7 +892,8 @@ class MultiModalDINOLightning(_LightningShaped):
         probe = LinearProbe(m.store, self._probe_kind(), m.output_dim,
                             getattr(m, "encoder_output_dim", None), lr=self.learning_rate,
                             act_dtype=_DT[self.precision],
-                            fusion_dropout=getattr(m.hp, "fusion_dropout", 0.3))
+                            fusion_dropout=getattr(m.hp, "fusion_dropout", 0.3),
+                            vit_attention=getattr(m, "vit_attention", "exact"))
         out = probe.run_epoch(traindata, validdata)
         self.log("val_loss", out["val_loss"])
         self.log("mlp_acc", out["mlp_acc"], on_epoch=True, prog_bar=True)
@@ -974,6 +986,9 @@ class UniModalDINO(_ArenaModule):
                 f"{encoder_class.__name__}: the MI355X engine runs ImageEncoder, SpectrogramEncoder, "
                 f"SpectrogramEncoderCentral, SpectrogramEncoderLSTM and SpectrogramEncoderViT")
         self.student_spec = enc
+        self.vit_attention = getattr(enc, "attention", "exact")
+        if self.vit_attention == "mfma" and _DT[precision] != torch.bfloat16:
+            raise ValueError(f"attention='mfma' is a bf16 kernel; it has no f32 mode (precision {precision!r})")
         self.projection_dim, self.output_dim = projection_dim, output_dim
         self.momentum, self.center_momentum, self.dropout = momentum, center_momentum, dropout
         self.device = _device(device)
@@ -986,8 +1001,9 @@ class UniModalDINO(_ArenaModule):
         if self.device.type == "cuda":
             self.engine = UniModalEngine(store, enc.kind, output_dim, projection_dim, self.hp,
                                          act_dtype=_DT[precision], cos_alpha=cosine_loss_alpha,
-                                         seed=seed)
+                                         seed=seed, vit_attention=self.vit_attention)
         self.student = _StudentView(self, enc.kind, output_dim, modality=enc.modality)
+        self.student.vit_attention = self.vit_attention
 
     arena_ranges = MultiModalDINO.arena_ranges
     update_teacher = MultiModalDINO.update_teacher

@@ -1263,6 +1263,36 @@ def mhsa_bwd(dout, q, k, v, lse, dq, dk, dv, ws, N, heads, T, dh, scale, bf16, d
                         drop_p, seed, _soff(seed_off), stream()))
 
 
+def mhsa_mfma_fwd(q, k, v, ctx, lse, N, heads, T, dh, scale, drop_p=0.0, seed=0, seed_off=None):
+    """mhsa_fwd's bf16 mode on the MFMA (avd_mhsa_mfma_fwd): same operands, lse and dropout mask."""
+    _mdims(N, heads, T, dh, drop_p)
+    E, R = heads * dh, N * T
+    a = _margs(((q, "q"), (k, "k"), (v, "v"), (ctx, "ctx")), R, E)
+    a.append(None if lse is None else _flat(lse, N * heads * T, "mhsa lse"))
+    _timed(f"mhsa_mfma_fwd[{N}x{heads}x{T}x{dh}]", 4 * 4 * R * E, 4 * N * heads * T * T * dh,
+           lambda: call("avd_mhsa_mfma_fwd", *a, N, heads, T, dh, scale, drop_p, seed, _soff(seed_off),
+                        stream()))
+
+
+def mhsa_mfma_bwd_ws(N, heads, T, dh):
+    _mdims(N, heads, T, dh, 0.0)
+    return lib.avd_mhsa_mfma_bwd_ws(N, heads, T, dh)
+
+
+def mhsa_mfma_bwd(dout, q, k, v, lse, dq, dk, dv, ws, N, heads, T, dh, scale, drop_p=0.0, seed=0,
+                  seed_off=None):
+    """dQ, dK, dV from dctx, Q, K, V and the forward's lse (avd_mhsa_mfma_bwd)."""
+    _mdims(N, heads, T, dh, drop_p)
+    E, R = heads * dh, N * T
+    a = _margs(((dout, "dout"), (q, "q"), (k, "k"), (v, "v")), R, E)
+    g = _margs(((dq, "dq"), (dk, "dk"), (dv, "dv")), R, E)
+    a += [_flat(lse, N * heads * T, "mhsa lse"), *g,
+          _flat(ws, mhsa_mfma_bwd_ws(N, heads, T, dh), "mhsa workspace")]
+    _timed(f"mhsa_mfma_bwd[{N}x{heads}x{T}x{dh}]", 4 * 7 * R * E, 10 * N * heads * T * T * dh,
+           lambda: call("avd_mhsa_mfma_bwd", *a, ws.numel(), N, heads, T, dh, scale, drop_p, seed,
+                        _soff(seed_off), stream()))
+
+
 def _ldims(rows, E):
     _need(rows >= 1 and 32 <= E <= LN_EMAX and E % 32 == 0,
           f"layer norm: E a multiple of 32 up to {LN_EMAX}, rows >= 1 (got {E}, {rows})")

@@ -85,8 +85,8 @@ class _UniEncoder:
     """One UNI_ENCODERS network under the state-dict prefix ``prefix``: a DINO model's
     ``student``, or a SimCLR tower (``image_encoder`` / ``audio_encoder``, spec.simclr_sd)."""
 
-    def __init__(self, kind, act, gm, prefix="student", out_dim=None):
-        self.enc = UniEncoder(kind, prefix, act, gm, out_dim=out_dim)
+    def __init__(self, kind, act, gm, prefix="student", out_dim=None, vit_attention="exact"):
+        self.enc = UniEncoder(kind, prefix, act, gm, out_dim=out_dim, vit_attention=vit_attention)
 
     def __call__(self, ws, st, x, N, train):
         if train:
@@ -160,9 +160,10 @@ class LinearProbe:
 
     def __init__(self, source, kind, D, E=None, lr=1e-4, weight_decay=0.01, act_dtype=F32,
                  fusion_dropout=0.3, seed=0, classifier_state=None, use_graph=True,
-                 prefix="student", towers=None, fusion="concat"):
+                 prefix="student", towers=None, fusion="concat", vit_attention="exact"):
         """prefix: the state-dict prefix of a unimodal ``kind`` ("student" for a DINO model; a
-        SimCLR tower's "image_encoder" / "audio_encoder").  towers: [(kind, prefix) of the image
+        SimCLR tower's "image_encoder" / "audio_encoder").  vit_attention: the attention kernels of
+        a ViT ``kind``'s tower (vit.ATTENTION_KINDS; the trained model's choice).  towers: [(kind, prefix) of the image
         tower, (kind, prefix) of the audio tower] for a late-fusion probe (``fusion``: concat /
         sum / mean; ``kind`` is then only a label and D the fused width)."""
         dev = source.device
@@ -179,12 +180,14 @@ class LinearProbe:
         self.ws = Workspace(dev)
         self.towers = towers is not None
         self.multimodal = self.towers or self.kind in MULTI_ENCODERS
+        if self.multimodal and vit_attention != "exact":
+            raise ValueError(f"vit_attention={vit_attention!r}: encoder {self.kind!r} has no ViT tower")
         if self.towers:
             self.enc = _TwoTower(towers, fusion, act_dtype, self.gm)
         elif self.multimodal:
             self.enc = _MultiEncoder(self.kind, E, D, act_dtype, self.gm, fusion_dropout)
         else:
-            self.enc = _UniEncoder(self.kind, act_dtype, self.gm, prefix, out_dim=D)
+            self.enc = _UniEncoder(self.kind, act_dtype, self.gm, prefix, out_dim=D, vit_attention=vit_attention)
             self.modality = uni_modality(self.kind)      # a conv-stack kind or a ViT one
         self.cls = ParamStore(classifier_sd(D), dev, seed=seed, has_teacher=False)
         if classifier_state is not None:

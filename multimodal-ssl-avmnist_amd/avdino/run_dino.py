@@ -36,6 +36,8 @@ MULTI_MODES = ["default", "semi_supervised", "mse", "infonce"]
 
 def parse_args(argv=None):
     from .models import MODEL_MAP, UNIMODAL_MODEL_MAP
+    from .spec import VIT_ENCODERS
+    from .vit import ATTENTION_KINDS
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     g = p.add_mutually_exclusive_group(required=True)
     g.add_argument("--model", choices=list(MODEL_MAP))
@@ -54,6 +56,9 @@ def parse_args(argv=None):
     p.add_argument("--probe-batches", type=int, default=4,
                    help="labelled batches for the epoch-end probe (synthetic data)")
     p.add_argument("--precision", default="bf16", choices=["bf16", "32"])
+    p.add_argument("--vit-attention", default="exact", choices=list(ATTENTION_KINDS),
+                   help="attention kernels of a ViT encoder: exact (f32 sums) or mfma (bf16 "
+                        "tensor-core kernels; --precision bf16 only)")
     p.add_argument("--synthetic", action="store_true", help="synthetic batches even if data exists")
     p.add_argument("--out", default=None, help="checkpoint directory (default: a temp dir)")
     p.add_argument("--downstream", action="store_true",
@@ -62,6 +67,12 @@ def parse_args(argv=None):
                    help="comma-separated seeds; one full fit (+ downstream) per seed from the same "
                         "initial weights (run_dino.py:346: seeds = [1, 2, 3])")
     a = p.parse_args(argv)
+    if a.vit_attention != "exact":
+        if a.precision != "bf16":
+            p.error(f"--vit-attention {a.vit_attention} is a bf16 kernel: it needs --precision bf16")
+        if a.unimodal_model not in VIT_ENCODERS:
+            p.error(f"--vit-attention {a.vit_attention} needs a model with a ViT tower "
+                    f"(--unimodal_model {' / '.join(VIT_ENCODERS)})")
     if a.unimodal_model and a.training_mode != "default":
         raise SystemExit(f"--training_mode '{a.training_mode}' is only compatible with --model "
                          f"(multimodal models).")   # run_dino.py:584-585
@@ -93,7 +104,10 @@ def build_model(args, config, device="cuda", group=None, seed=None):
         return cls(encoder_class=MODEL_MAP[args.model], encoder_output_dim=h["encoder_output_dim"],
                    student_temperature=h["student_temperature"], use_mixed_precision=True,
                    group=group, **common)
-    return UniModalDINOLightning(encoder_class=UNIMODAL_MODEL_MAP[args.unimodal_model],
+    # the default leaves encoder_kwargs (and so the saved hyper-parameters) as they always were
+    vit_attention = getattr(args, "vit_attention", "exact")
+    kwargs = None if vit_attention == "exact" else {"attention": vit_attention}
+    return UniModalDINOLightning(encoder_class=UNIMODAL_MODEL_MAP[args.unimodal_model], encoder_kwargs=kwargs,
                                  cosine_loss_alpha=h["cosine_loss_alpha"], **common)
 
 

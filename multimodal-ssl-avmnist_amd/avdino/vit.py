@@ -7,6 +7,10 @@ The tower knows nothing of an engine: it takes a workspace, a parameter store, a
 its dimensions, so the unimodal encoder (embed_dim 512) and a later multimodal one
 (embed_dim = encoder_output_dim) instantiate the same class.
 
+``attention`` picks the attention kernels (ATTENTION_KINDS): "exact" = avd_mhsa_* (csrc/vit.hip, f32
+sums on the VALU in both modes, the default) or "mfma" = avd_mhsa_mfma_* (csrc/mhsa_mfma.hip, bf16
+tensor-core kernels; bf16 activations only).  Same operands, lse, seeds and masks either way.
+
 Dropout sites and seeds.  A layer has four: "attn" on the attention probabilities, "sa" on the
 attention block's output (dropout1), "ff1" inside the MLP (dropout), "ff2" on the MLP's output
 (dropout2).  ``seeds`` = (p, base, seed_off, role): site s (0 attn, 1 sa, 2 ff1, 3 ff2) of layer
@@ -33,6 +37,7 @@ from . import ops
 F32 = torch.float32
 SITES = ("attn", "sa", "ff1", "ff2")
 MAX_DEPTH = 16              # layers a role's 64 site numbers cover
+ATTENTION_KINDS = ("exact", "mfma")     # avd_mhsa_* (f32 VALU sums) | avd_mhsa_mfma_* (bf16 MFMA)
 
 
 def site_seed(base, role, layer, site):
@@ -45,7 +50,13 @@ def tokens(hw, patch):
 
 class ViTTower:
     def __init__(self, prefix, hw, patch, embed_dim, depth, heads, act_dtype, gemm_mode, mlp_ratio=4,
-                 eps=1e-5):
+                 eps=1e-5, attention="exact"):
+        if attention not in ATTENTION_KINDS:
+            raise ValueError(f"ViT: attention must be one of {ATTENTION_KINDS} (got {attention!r})")
+        if attention == "mfma" and act_dtype != torch.bfloat16:
+            raise ValueError("ViT: attention='mfma' is a bf16 kernel; it has no f32 mode "
+                             f"(activation dtype {act_dtype})")
+        self.attention = attention
         if hw % patch != 0:
             raise ValueError(f"ViT: the map size {hw} is no multiple of the patch size {patch}")
         if embed_dim % heads != 0 or embed_dim // heads not in ops.MHSA_HEAD_DIMS:
@@ -87,6 +98,24 @@ class ViTTower:
         p, base, off, role = seeds
         return float(p), site_seed(base, role, i, site), off
 
+    # ---- the chosen attention family
+    def _mhsa_fwd(self, q, k, v, ctx, lse, N, p, seed, off):
+        if self.attention == "mfma":
+            return ops.mhsa_mfma_fwd(q, k, v, ctx, lse, N, self.heads, self.T, self.dh, self.scale, p, seed, off)
+        return ops.mhsa_fwd(q, k, v, ctx, lse, N, self.heads, self.T, self.dh, self.scale, self.bf16, p, seed,
+                            off)
+
+    def _mhsa_bwd_ws(self, N):
+        ws = ops.mhsa_mfma_bwd_ws if self.attention == "mfma" else ops.mhsa_bwd_ws
+        return ws(N, self.heads, self.T, self.dh)
+
+    def _mhsa_bwd(self, dout, q, k, v, lse, dq, dk, dv, ws, N, p, seed, off):
+        if self.attention == "mfma":
+            return ops.mhsa_mfma_bwd(dout, q, k, v, lse, dq, dk, dv, ws, N, self.heads, self.T, self.dh,
+                                     self.scale, p, seed, off)
+        return ops.mhsa_bwd(dout, q, k, v, lse, dq, dk, dv, ws, N, self.heads, self.T, self.dh, self.scale,
+                            self.bf16, p, seed, off)
+
     # ---- forward
     def forward(self, ws, store, tag, x, N, train, seeds=None):
         """x: the staged one-channel maps [N, hw, hw] (act dtype).  Returns (cls [N, E] f32: the
@@ -113,8 +142,8 @@ class ViTTower:
             att = c["ctx"] = buf("ctx", R * E)
             lse = c["lse"] = buf("lse", N * heads * T) if train else None
             p, seed, off = self._seed(seeds, i, "attn")
-            ops.mhsa_fwd((qkv, 0, 3 * E), (qkv, E, 3 * E), (qkv, 2 * E, 3 * E), (att, 0, E), lse, N, heads,
-                         T, dh, self.scale, self.bf16, p, seed, off)
+            self._mhsa_fwd((qkv, 0, 3 * E), (qkv, E, 3 * E), (qkv, 2 * E, 3 * E), (att, 0, E), lse, N, p, seed,
+                           off)
             ops.linear_fwd(att, st[self._key(i, "self_attn.out_proj.weight")],
                            st[self._key(i, "self_attn.out_proj.bias")], a, R, mode=self.gm)
             h1 = c["h1"] = buf("h1", R * E)
@@ -168,7 +197,7 @@ class ViTTower:
         dt = ws.get("vit.dt", R * E)
         dqkv = ws.get("vit.dqkv", R * 3 * E)
         df = ws.get("vit.df", R * F)
-        aws = ws.get("vit.aws", ops.mhsa_bwd_ws(N, heads, T, dh))
+        aws = ws.get("vit.aws", self._mhsa_bwd_ws(N))
         # the final LayerNorm saw the cls rows only: every other token row's gradient is zero
         dhb.zero_()
         ops.ln_bwd(dcls.reshape(-1), ctx["zf"], ctx["meanf"], ctx["rstdf"], st[f"{pre}.transformer.norm.weight"],
@@ -197,9 +226,8 @@ class ViTTower:
                            mode=self.gm)
             p, seed, off = self._seed(seeds, i, "attn")
             qkv = c["qkv"]
-            ops.mhsa_bwd((dt, 0, E), (qkv, 0, 3 * E), (qkv, E, 3 * E), (qkv, 2 * E, 3 * E), c["lse"],
-                         (dqkv, 0, 3 * E), (dqkv, E, 3 * E), (dqkv, 2 * E, 3 * E), aws, N, heads, T, dh,
-                         self.scale, self.bf16, p, seed, off)
+            self._mhsa_bwd((dt, 0, E), (qkv, 0, 3 * E), (qkv, E, 3 * E), (qkv, 2 * E, 3 * E), c["lse"],
+                           (dqkv, 0, 3 * E), (dqkv, E, 3 * E), (dqkv, 2 * E, 3 * E), aws, N, p, seed, off)
             ops.linear_bwd(dqkv, c["x"], st[k("self_attn.in_proj_weight")],
                            g(k("self_attn.in_proj_weight")), g(k("self_attn.in_proj_bias")), dh1, R,
                            mode=self.gm)

@@ -1,6 +1,6 @@
 """Time the ViT kernels alone and the whole spectrogram_vit training step, bf16, on one MI355X.
 
-    python tools/vitbench.py [--reps 20] [--warmup 5] [--batch 128] [--out FILE]
+    python tools/vitbench.py [--reps 20] [--warmup 5] [--batch 128] [--rounds 2] [--out FILE]
 
 Two kinds of measurement, each in a fresh child process (its own HIP context and allocator) under
 its own time limit; the parent stops at the first child that fails:
@@ -11,10 +11,13 @@ its own time limit; the parent stops at the first child that fails:
          backward -- operations of the algorithm, computed here from the shapes) against the bf16
          MFMA peak and against the f32 vector rate the present kernels run at, and the time of
          the same problem through avd_xattn_fwd / avd_xattn_bwd, called per head with dirs = 1,
-         groups = N, a zero x and scale = dh^-0.5 (the time of its four calls, summed);
+         groups = N, a zero x and scale = dh^-0.5 (the time of its four calls, summed); and, in
+         the same process at the same shape, avd_mhsa_mfma_fwd / _bwd (p = 0 and p = 0.1) with
+         the same FLOP formulas and their ratios to both;
   step   the graph-replayed UniModalEngine step, 2 + 4 views, D = 256, P = 128, for
-         spectrogram_vit and, on the same box in the same run, spectrogram_simple and
-         spectrogram_lstm at the same B.
+         spectrogram_vit with --attention exact and mfma, alternating, ``--rounds`` times each (the
+         repeated lines show the run-to-run spread), and, on the same box in the same run,
+         spectrogram_simple and spectrogram_lstm at the same B.
 Every figure is the mean of HIP events around each of ``reps`` (>= 20) launches / replays after
 ``warmup`` untimed ones, with min and max.  Lines are appended to ``--out``."""
 import argparse
@@ -69,12 +72,21 @@ def child_ops(args):
         res[name + "_bwd"] = _timed(lambda: ops.mhsa_bwd((do, 0, E), q, k, v, lse, dq, dk, dv, aws, N, HEADS, T, DH,
                                                          scale, True, p, 11), w, r)
     assert bool(torch.isfinite(ctx).all()) and bool(torch.isfinite(dqkv).all())
+    mws = torch.empty(ops.mhsa_mfma_bwd_ws(N, HEADS, T, DH), device=dev)
+    for name, p in (("mhsa_mfma", 0.0), ("mhsa_mfma_drop0.1", 0.1)):
+        res[name + "_fwd"] = _timed(lambda: ops.mhsa_mfma_fwd(q, k, v, (ctx, 0, E), lse, N, HEADS, T, DH, scale, p, 11),
+                                    w, r)
+        res[name + "_bwd"] = _timed(lambda: ops.mhsa_mfma_bwd((do, 0, E), q, k, v, lse, dq, dk, dv, mws, N, HEADS, T,
+                                                              DH, scale, p, 11), w, r)
+    assert bool(torch.isfinite(ctx).all()) and bool(torch.isfinite(dqkv).all())
     fl_f, fl_b = 4 * N * HEADS * T * T * DH, 10 * N * HEADS * T * T * DH
     for tag, fl in (("fwd", fl_f), ("bwd", fl_b)):
-        rate = fl / (res["mhsa_" + tag]["ms"] * 1e-3)
-        res[f"mhsa_{tag}_tflops"] = round(rate / 1e12, 2)
-        res[f"mhsa_{tag}_share_of_bf16_mfma_peak"] = round(rate / PEAK_BF16_MFMA, 4)
-        res[f"mhsa_{tag}_share_of_f32_vector_rate"] = round(rate / PEAK_F32_VALU, 4)
+        for fam in ("mhsa", "mhsa_mfma"):
+            rate = fl / (res[f"{fam}_{tag}"]["ms"] * 1e-3)
+            res[f"{fam}_{tag}_tflops"] = round(rate / 1e12, 2)
+            res[f"{fam}_{tag}_share_of_bf16_mfma_peak"] = round(rate / PEAK_BF16_MFMA, 4)
+            if fam == "mhsa":
+                res[f"mhsa_{tag}_share_of_f32_vector_rate"] = round(rate / PEAK_F32_VALU, 4)
     # the same problem through the cross-attention kernel: one call per head
     zero = torch.zeros(R * E, device=dev)
     xlse = torch.empty(HEADS, N * T, device=dev)
@@ -97,6 +109,9 @@ def child_ops(args):
     res["xattn_bwd_4_heads"] = _timed(xb, w, r)
     res["mhsa_over_xattn_fwd"] = round(res["mhsa_fwd"]["ms"] / res["xattn_fwd_4_heads"]["ms"], 2)
     res["mhsa_over_xattn_bwd"] = round(res["mhsa_bwd"]["ms"] / res["xattn_bwd_4_heads"]["ms"], 2)
+    for tag in ("fwd", "bwd"):
+        res[f"mhsa_mfma_over_xattn_{tag}"] = round(res[f"mhsa_mfma_{tag}"]["ms"] / res[f"xattn_{tag}_4_heads"]["ms"], 4)
+        res[f"mhsa_over_mhsa_mfma_{tag}"] = round(res[f"mhsa_{tag}"]["ms"] / res[f"mhsa_mfma_{tag}"]["ms"], 2)
     # LayerNorm and GELU at the model's row counts
     x, rr, y, z = (torch.randn(R * E, generator=g, device=dev) for _ in range(4))
     gam, bet = torch.ones(E, device=dev), torch.zeros(E, device=dev)
@@ -131,7 +146,7 @@ def child_step(args):
             t = store[f"student.encoder.0.{k}"]
             t.copy_(torch.randn(t.shape, generator=gen0) * 0.02)
             store[f"teacher.encoder.0.{k}"].copy_(t)
-    eng = UniModalEngine(store, args.model, D, P, Hyper(), act_dtype=torch.bfloat16)
+    eng = UniModalEngine(store, args.model, D, P, Hyper(), act_dtype=torch.bfloat16, vit_attention=args.attention)
     eng.use_graph = True
     gen = torch.Generator(device=dev).manual_seed(1234)
 
@@ -149,7 +164,8 @@ def child_step(args):
     assert len(eng.graph.graphs) == 1, "the timed steps must be graph replays"
     lv = float(eng.last["loss"].item())
     assert lv == lv, "loss is NaN"
-    print(json.dumps({"what": "step", "model": args.model, "B": B, "views": G + L, "step": r,
+    print(json.dumps({"what": "step", "model": args.model, "attention": args.attention, "B": B, "views": G + L,
+                      "step": r,
                       "samples_per_s": round(B / r["ms"] * 1e3, 1), "loss": round(lv, 5),
                       "workspace_GiB": round(eng.ws.nbytes() / 2 ** 30, 2)}), flush=True)
 
@@ -162,15 +178,21 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--what", default=None, help="(child) ops | step")
     ap.add_argument("--model", default="spectrogram_vit", help="(child) the encoder of a step child")
+    ap.add_argument("--attention", default="exact", choices=["exact", "mfma"],
+                    help="(child) the ViT attention kernels of a step child")
+    ap.add_argument("--rounds", type=int, default=2, help="exact / mfma spectrogram_vit step pairs")
     args = ap.parse_args()
     if args.reps < 20:
         ap.error("--reps must be at least 20")
     if args.what:
         return {"ops": child_ops, "step": child_step}[args.what](args)
-    jobs = [("ops", None)] + [("step", m) for m in ("spectrogram_vit", "spectrogram_simple", "spectrogram_lstm")]
-    for what, model in jobs:
+    jobs = [("ops", None, None)]
+    jobs += [("step", "spectrogram_vit", att) for _ in range(max(args.rounds, 1)) for att in ("exact", "mfma")]
+    jobs += [("step", m, "exact") for m in ("spectrogram_simple", "spectrogram_lstm")]
+    for what, model, att in jobs:
         cmd = [sys.executable, os.path.abspath(__file__), "--what", what, "--batch", str(args.batch),
-               "--reps", str(args.reps), "--warmup", str(args.warmup)] + (["--model", model] if model else [])
+               "--reps", str(args.reps), "--warmup", str(args.warmup)]
+        cmd += ["--model", model, "--attention", att] if model else []
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
             rc, tail = p.returncode, (p.stdout + p.stderr)[-800:]
@@ -185,7 +207,7 @@ def main():
             continue
         # any failure, abort, signal or time limit: nothing more is started on the device
         sys.stderr.write(tail)
-        raise SystemExit(f"child {what}/{model} failed with {rc}: stopping")
+        raise SystemExit(f"child {what}/{model}/{att} failed with {rc}: stopping")
 
 
 if __name__ == "__main__":
